@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): Gauss-Newton iterations/s + converged systems/s on a batch of
 100 000 independent 32-constraint f64 sketches ("ring16", cfg3) per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One *step* = one pass of the hot path over the HBM-resident batch: `fx_system_solve_device`
 (== fiksi `System::solve(SolvingOptions::DEFAULT)` for every sketch: RMS scaling, LCG perturbation,
@@ -17,7 +17,11 @@ contiguous shard of 100k / N systems (workloads.shard). At N = 1 the line also c
 measured time of the 1/2, 1/4 and 1/8 shards on this GPU, i.e. the strong-scaling curve before an 8-GPU node
 shows up.
 
-Prints ONE JSON line (rank 0). Besides the contract fields it carries
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, the counters of the timed steps, `solve_kernel` from the same launches) and nothing else.
+--dump-outputs DIR writes what the last timed step computed (rank 0's shard: solved variables and result records, see
+dump_outputs) for output-by-output comparison of two builds; the inputs are seeded, the same from run to run.
+--full also measures everything beside the headline, each in runs of its own after the timed steps:
   roofline      — the Jacobian-assembly kernel (K1, `eval_rows_kernel<true>`), the HBM-bound kernel the
                   north-star prices against the 8 TB/s roofline, ON A 500k-SYSTEM BATCH whose footprint (0.97 GB
                   moved per launch) is 3.8x the 256 MiB Infinity Cache. `achieved` / `frac` = the bytes a launch
@@ -58,21 +62,43 @@ F64_VECTOR_PEAK_TFLOPS = 78.6  # MI355X f64 vector (non-matrix) peak
 FLOPS_PER_TRIAL = 32 ** 3 / 3 + 2 * 32 ** 2 + 2 * 408 + 60 * 32  # ring16 component, see solve_kernel below
 
 
+def _count(least: int):
+    def parse_count(s: str) -> int:
+        v = int(s)
+        if v < least:
+            raise argparse.ArgumentTypeError(f"must be at least {least}")
+        return v
+    return parse_count
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=_count(1), default=20, help="timed steps")
+    ap.add_argument("--warmup", type=_count(0), default=3, help="untimed steps before them")
     ap.add_argument("--systems", type=int, default=SYSTEMS_PER_GPU, help="systems per GPU (default: the BASELINE config)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --systems per GPU (default); strong: --systems in total, split over the GPUs (cfg4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="the headline + roofline only (no side workloads)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="systems in the CPU-baseline sample (0 = auto)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, float64, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the side workloads and the CPU baseline (a plain run: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--quick", action="store_true", help="with --full: the headline + roofline only (no side workloads)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="with --full: systems in the CPU-baseline sample (0 = auto)")
     ap.add_argument("--host-threads", type=int, default=0,
                     help="host threads of the sparse path for batches of several large Systems (0 = library default 8; the "
                          "profiled runs of tools/collect_profiles.sh use 1: rocprofv3 --kernel-trace crashes under concurrent launches)")
     return ap.parse_args()
+
+
+def build_or_use_built(graft) -> None:
+    """graft.build() compiles what is stale, under a lock file it opens in the tree. A tree built beforehand may be
+    read-only to the user who benchmarks it: nothing can be built there, so the native code built in it is used."""
+    try:
+        graft.build()
+    except PermissionError as e:
+        print(f"bench.py: cannot write in the tree ({e}); using the native code already built in it", file=sys.stderr)
 
 
 def relaunch_under_torchrun(args) -> int:
@@ -99,8 +125,8 @@ def main() -> int:
 
     import __graft_entry__ as graft
 
-    graft.build()
-    import fiksi_amd
+    build_or_use_built(graft)
+    import fiksi_amd  # (raises if the native library is missing: there is no fallback)
     from fiksi_amd import abi, distributed, workloads
 
     dist = None
@@ -165,6 +191,8 @@ def main() -> int:
     elapsed = time.perf_counter() - t0
 
     res = db.get_results()
+    if args.dump_outputs and rank == 0:  # before anything else solves on this batch
+        dump_outputs(args.dump_outputs, db.get_vars(), batch["var_off"], res)
     converged = int(np.count_nonzero(res["sse_unscaled"] < 1e-4))  # fiksi_bench.rs:65-72
     accepted = int(res["accepted"].sum())
     trials = int(res["trials"].sum())
@@ -176,10 +204,11 @@ def main() -> int:
     elapsed, (converged, accepted, trials, total_sys) = distributed.reduce_throughput(
         dist, elapsed, [converged, accepted, trials, n_sys], device=reduce_device)
 
-    # ---- K1 (Jacobian assembly) on the same resident batch, HIP-event timed ----------------
-    k1_ms, _, k1_launches = _time_k1(ctx, db)
-    k1_bytes = workloads.k1_algorithmic_bytes(batch, db.nnz, one_structure=True)  # 1920 B x systems for ring16 (one structure)
-    k1_gbs = k1_bytes / (k1_ms * 1e-3) / 1e9
+    # ---- --full: K1 (Jacobian assembly) on the same resident batch, HIP-event timed ----------
+    if args.full:
+        k1_ms, _, k1_launches = _time_k1(ctx, db)
+        k1_bytes = workloads.k1_algorithmic_bytes(batch, db.nnz, one_structure=True)  # 1920 B x systems for ring16 (one structure)
+        k1_gbs = k1_bytes / (k1_ms * 1e-3) / 1e9
 
     out = None
     if rank == 0:
@@ -221,7 +250,6 @@ def main() -> int:
                 "parallelism": f"dp{world} (independent systems sharded, no data-path collective)",
                 "device": ctx.name(),
             },
-            "roofline": None,  # filled below: the HBM figure needs the 500k-System batch (weak scaling, N = 1) or falls back
             "solve_kernel": {
                 "kernel": ("lm_solve_grouped_c_kernel (fused scale+perturb+assembly+LM+write-back, four Systems per wavefront: one per "
                            "DPP row; the build for batches of one structure — lists shared by the wavefront, Jt J by its pattern, "
@@ -245,39 +273,41 @@ def main() -> int:
                         "grouped kernel's general build (one wavefront per SIMD)",
             },
         }
-        in_cache = {
-            "systems": n_sys, "achieved": k1_gbs, "frac": k1_gbs / HBM_PEAK_GBS, "avg_launch_ms": k1_ms, "launches": k1_launches,
-            "algorithmic_bytes_per_launch": k1_bytes, "traffic": pmc_traffic("eval_rows_kernel<true", n_sys),
-            "note": "194 MB per launch: under the 256 MiB Infinity Cache, so this is not an HBM rate",
-        }
-        in_cache["frac_by_counter_bytes"] = None if in_cache["traffic"] is None else in_cache["traffic"] / (k1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        roof = {
-            "kernel": "eval_rows_kernel<true> (K1 Jacobian assembly: residuals + CSR J values; "
-                      "fx_eval_residual_jacobian_device on a resident batch)",
-            "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "traffic_source": "profiles/round5_pmc_traffic*.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate "
-                              "passes; read bytes = 2 x FETCH_SIZE KiB per the gfx950 correction, checked on a "
-                              "known-byte kernel with K1's access widths: tools/probes/fetch_calib.hip)",
-        }
-        if world == 1 and args.scaling == "weak":
-            roof.update(k1_past_l3(ctx, workloads))
-        else:  # (N > 1 or the strong-scaling mode: the timed batch's own figure, flagged)
-            roof.update({"achieved": k1_gbs, "frac": k1_gbs / HBM_PEAK_GBS, "traffic": in_cache["traffic"], "workload_systems": n_sys,
-                         "avg_launch_ms": k1_ms, "algorithmic_bytes_per_launch": k1_bytes,
-                         "note": "in-cache figure (the 500k-System HBM measurement runs at N = 1, weak scaling)"})
-        roof["in_cache"] = in_cache
-        out["roofline"] = roof
         out["solve_kernel"].update(sq_counters("lm_solve_grouped", FLOPS_PER_TRIAL * trials_per_step))
-        if world == 1 and not args.quick:
-            out["host_path"] = host_path(ctx, batch, np)
-            out["step_solvers"] = step_solvers(ctx, db, abi, np, n_sys, solve_ms)
-            out["cfg4_prediction"] = cfg4_prediction(ctx, abi, workloads, batch, solve_ms)
-            out["other_workloads"] = other_workloads(ctx, abi, workloads, np, n_sys)
-            out["large_systems"] = large_systems(ctx, abi, workloads, np)
-            out["reference_bench_group"] = reference_bench_group(ctx, abi, workloads, np)
-            out["decomposers_single_triangle"] = decomposers_single_triangle(ctx)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(batch, args.cpu_sample)
+        if args.full:
+            in_cache = {
+                "systems": n_sys, "achieved": k1_gbs, "frac": k1_gbs / HBM_PEAK_GBS, "avg_launch_ms": k1_ms, "launches": k1_launches,
+                "algorithmic_bytes_per_launch": k1_bytes, "traffic": pmc_traffic("eval_rows_kernel<true", n_sys),
+                "note": "194 MB per launch: under the 256 MiB Infinity Cache, so this is not an HBM rate",
+            }
+            in_cache["frac_by_counter_bytes"] = None if in_cache["traffic"] is None else in_cache["traffic"] / (k1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+            roof = {
+                "kernel": "eval_rows_kernel<true> (K1 Jacobian assembly: residuals + CSR J values; "
+                          "fx_eval_residual_jacobian_device on a resident batch)",
+                "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "traffic_source": "profiles/round5_pmc_traffic*.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate "
+                                  "passes; read bytes = 2 x FETCH_SIZE KiB per the gfx950 correction, checked on a "
+                                  "known-byte kernel with K1's access widths: tools/probes/fetch_calib.hip)",
+            }
+            # the HBM figure needs the 500k-System batch (weak scaling, N = 1)
+            if world == 1 and args.scaling == "weak":
+                roof.update(k1_past_l3(ctx, workloads))
+            else:  # (N > 1 or the strong-scaling mode: the timed batch's own figure, flagged)
+                roof.update({"achieved": k1_gbs, "frac": k1_gbs / HBM_PEAK_GBS, "traffic": in_cache["traffic"], "workload_systems": n_sys,
+                             "avg_launch_ms": k1_ms, "algorithmic_bytes_per_launch": k1_bytes,
+                             "note": "in-cache figure (the 500k-System HBM measurement runs at N = 1, weak scaling)"})
+            roof["in_cache"] = in_cache
+            out["roofline"] = roof
+            if world == 1 and not args.quick:
+                out["host_path"] = host_path(ctx, batch, np)
+                out["step_solvers"] = step_solvers(ctx, db, abi, np, n_sys, solve_ms)
+                out["cfg4_prediction"] = cfg4_prediction(ctx, abi, workloads, batch, solve_ms)
+                out["other_workloads"] = other_workloads(ctx, abi, workloads, np, n_sys)
+                out["large_systems"] = large_systems(ctx, abi, workloads, np)
+                out["reference_bench_group"] = reference_bench_group(ctx, abi, workloads, np)
+                out["decomposers_single_triangle"] = decomposers_single_triangle(ctx)
+            if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+                out["cpu_baseline"] = cpu_baseline(batch, args.cpu_sample)
         print(json.dumps(out), flush=True)
 
     db.free()
@@ -287,6 +317,33 @@ def main() -> int:
         dist.destroy_process_group()
     return 0
 
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, vars_, var_off, res, budget: int = DUMP_BUDGET_BYTES):
+    """What a caller of the timed path receives after a solve, as DIR/<name>.npy in float64: `vars` (the solved
+    variables of the Systems written, flat, in System order), `result_<field>` (one per field of the result record) and
+    `systems` (the indices of the Systems written). Every System when that fits in `budget` bytes (the 100k headline
+    batch: 33 MB); past it, a fixed, seeded sample of the Systems, the same for the same batch."""
+    import numpy as np
+
+    var_off = np.asarray(var_off, dtype=np.int64)
+    n = len(res)
+    lens = var_off[1:] - var_off[:-1]
+    per_system = 8 * (lens + len(res.dtype.names) + 1)
+    idx = np.arange(n)
+    if per_system.sum() > budget:
+        order = np.random.default_rng(20261015).permutation(n)
+        idx = np.sort(order[: np.searchsorted(np.cumsum(per_system[order]), budget, side="right")])
+        lens_i = lens[idx]
+        starts = np.repeat(var_off[idx] - np.cumsum(lens_i) + lens_i, lens_i)
+        vars_ = vars_[starts + np.arange(int(lens_i.sum()))]
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"vars": vars_, "systems": idx}
+    arrays.update({"result_" + f: res[f][idx] for f in res.dtype.names})
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _time_k1(ctx, db, groups: int = 10, per_group: int = 6):

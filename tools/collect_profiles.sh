@@ -78,5 +78,5 @@ tools/probes/rw_mix_probe.bin 2>> $OUT/misc.err | tail -1 > $OUT/${TAG}_hbm_rw_m
 tools/probes/valu_cost_probe.bin 2>> $OUT/misc.err | tail -1 > $OUT/${TAG}_valu_cost.json
 echo "[collect] plain bench line (it quotes the counter files: this run's go to profiles/ first)"
 cp $OUT/${TAG}_pmc_traffic.json $OUT/${TAG}_pmc_traffic_500k.json $OUT/${TAG}_pmc_traffic_500k_mixed.json $OUT/${TAG}_pmc_sq.json $ROOT/profiles/ 2>/dev/null || true
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/${TAG}_bench.json

@@ -1084,13 +1084,14 @@ __device__ __forceinline__ void grouped_body(const DeviceBatch& b, const LmParam
 #pragma unroll
                     for (int q = 0; q < NC; ++q) invd[q] = T(1);
                     bool bad = false;
-                    RBlock<NC, T, 0, UNITS>::factor(a, invd, bad, hl, kmax);
+                    T acc[NC];
+                    RBlock<NC, T, 0, UNITS>::template factor<false>(a, invd, acc, bad, hl, kmax);
                     stamp(GH_FACTOR);
                     if (bad) {  // lm.rs:134-137
                         code = LC_SINGULAR;
                         go = false;
                     } else {
-                        T acc[NC], invd2[NC];
+                        T invd2[NC];
 #pragma unroll
                         for (int q = 0; q < NC; ++q) {
                             acc[q] = rhs_l[q];

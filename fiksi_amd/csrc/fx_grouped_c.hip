@@ -546,18 +546,21 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
 #pragma unroll
                     for (int q = 0; q < NC; ++q) invd[q] = T(1);
                     bool bad = false;
-                    RBlock<NC, T, 0, false>::factor(a, invd, bad, hl, N);
+                    // (two columns per lane: the forward substitution runs inside the factorization, a step behind each pivot;
+                    // the one-column build keeps its own pass, where the fused form cost it scratch)
+                    constexpr bool FWD = NC == 2;
+                    T acc[NC];
+#pragma unroll
+                    for (int q = 0; q < NC; ++q) acc[q] = rhs_l[q];
+                    RBlock<NC, T, 0, false>::template factor<FWD>(a, invd, acc, bad, hl, N);
                     if (bad) {  // lm.rs:134-137
                         code = LC_SINGULAR;
                         go = false;
                     } else {
-                        T acc[NC], invd2[NC];
+                        T invd2[NC];
 #pragma unroll
-                        for (int q = 0; q < NC; ++q) {
-                            acc[q] = rhs_l[q];
-                            invd2[q] = invd[q] * invd[q];
-                        }
-                        RBlock<NC, T, 0, false>::forward(a, invd, acc, hl, N);
+                        for (int q = 0; q < NC; ++q) invd2[q] = invd[q] * invd[q];
+                        if constexpr (!FWD) RBlock<NC, T, 0, false>::forward(a, invd, acc, hl, N);
                         RBlock<NC, T, N / 8 - 1, false>::backward(a, invd2, acc, hl, N);
 #pragma unroll
                         for (int q = 0; q < NC; ++q) delta[q] = ((uint32_t)(hl + RS * q) < nfree) ? acc[q] * invd2[q] : T(0);

@@ -80,7 +80,11 @@ template <int NC, typename T, int K, bool BOUNDED>
 struct RStep {  // one column step of the factorization / of a triangular solve
     static constexpr int N = RS * NC;
     static constexpr int KA = K / RS, KL = K % RS;  // array and lane of column K
-    static __device__ __forceinline__ void factor(T (&a)[NC][N], T (&invd)[NC], bool& bad, int hl, int kmax) {
+    // FWD: forward substitution step K right behind factor step K (`forward` below, the same operations on the same
+    // operands: what it reads — a[.][K] of the lanes above K and invd of lane K, which is rs — is final once factor step K
+    // is done, and no later factor step writes it)
+    template <bool FWD>
+    static __device__ __forceinline__ void factor(T (&a)[NC][N], T (&invd)[NC], T (&acc)[NC], bool& bad, int hl, int kmax) {
         {
         const T piv = rbcast<KL>(a[KA][K]);
         bad = bad || !(piv > T(0)) || !(piv < Lim<T>::huge());
@@ -110,6 +114,7 @@ struct RStep {  // one column step of the factorization / of a triangular solve
                     else fnma_rbcast<KL>(a[q][i], a[KA][i], mul[q]);
                 }
             }
+            if constexpr (FWD) forward_dpp(a, rs, acc, hl);  // (t = acc * invd of column K's lane, where invd = rs)
             // (inline asm is opaque to the hazard recogniser: a DPP read needs two wait states after a VALU write of
             // its source, and the next pivot broadcast may read what the last instruction above wrote)
             asm volatile("s_nop 1");
@@ -126,22 +131,27 @@ struct RStep {  // one column step of the factorization / of a triangular solve
                     a[q][i] = fma(-aik, mul[q], a[q][i]);
                 }
             }
+            static_assert(!FWD, "the 48-column build substitutes in a pass of its own");
         }
         }
     }
     // acc[q] -= a[q][K] * y_K, y_K = (acc * invd) of column K's lane: the broadcast is the DPP operand of the
     // multiply-add; lanes that must not take part get a zero factor.
+    static __device__ __forceinline__ void forward_dpp(const T (&a)[NC][N], T invd_k, T (&acc)[NC], int hl) {
+        T t = acc[KA] * invd_k;
+        dpp_settle(t);
+#pragma unroll
+        for (int q = NC - 1; q >= KA; --q) {
+            if (q == KA && KL == RS - 1) continue;
+            const T w = (q > KA || hl > KL) ? a[q][K] : T(0);
+            fnma_rbcast<KL>(acc[q], t, w);
+        }
+    }
     static __device__ __forceinline__ void forward(const T (&a)[NC][N], const T (&invd)[NC], T (&acc)[NC], int hl, int kmax) {
         {
         T t = acc[KA] * invd[KA];
         if constexpr (NC <= 2) {
-            dpp_settle(t);
-#pragma unroll
-            for (int q = NC - 1; q >= KA; --q) {
-                if (q == KA && KL == RS - 1) continue;
-                const T w = (q > KA || hl > KL) ? a[q][K] : T(0);
-                fnma_rbcast<KL>(acc[q], t, w);
-            }
+            forward_dpp(a, invd[KA], acc, hl);
         } else {
             const T yk = rbcast<KL>(t);
 #pragma unroll
@@ -183,9 +193,9 @@ struct RStep {  // one column step of the factorization / of a triangular solve
 template <int NC, typename T, int KB, bool BOUNDED>
 struct RBlock {
     static constexpr int N = RS * NC;
-    template <int... I>
-    static __device__ __forceinline__ void factor8(T (&a)[NC][N], T (&invd)[NC], bool& bad, int hl, int kmax, std::integer_sequence<int, I...>) {
-        (RStep<NC, T, 8 * KB + I, BOUNDED>::factor(a, invd, bad, hl, kmax), ...);
+    template <bool FWD, int... I>
+    static __device__ __forceinline__ void factor8(T (&a)[NC][N], T (&invd)[NC], T (&acc)[NC], bool& bad, int hl, int kmax, std::integer_sequence<int, I...>) {
+        (RStep<NC, T, 8 * KB + I, BOUNDED>::template factor<FWD>(a, invd, acc, bad, hl, kmax), ...);
     }
     template <int... I>
     static __device__ __forceinline__ void forward8(const T (&a)[NC][N], const T (&invd)[NC], T (&acc)[NC], int hl, int kmax, std::integer_sequence<int, I...>) {
@@ -195,9 +205,12 @@ struct RBlock {
     static __device__ __forceinline__ void backward8(const T (&a)[NC][N], const T (&invd2)[NC], T (&acc)[NC], int hl, int kmax, std::integer_sequence<int, I...>) {
         (RStep<NC, T, 8 * KB + 7 - I, BOUNDED>::backward(a, invd2, acc, hl, kmax), ...);
     }
-    static __device__ __forceinline__ void factor(T (&a)[NC][N], T (&invd)[NC], bool& bad, int hl, int kmax) {
-        if (!BOUNDED || 8 * KB < kmax) factor8(a, invd, bad, hl, kmax, std::make_integer_sequence<int, 8>{});
-        if constexpr (8 * KB + 8 < N) RBlock<NC, T, KB + 1, BOUNDED>::factor(a, invd, bad, hl, kmax);
+    // FWD (NC <= 2): the forward substitution of acc rides along, step by step (RStep::factor); a result the caller throws
+    // away when the factorization reports `bad`, as it skips the forward pass then
+    template <bool FWD>
+    static __device__ __forceinline__ void factor(T (&a)[NC][N], T (&invd)[NC], T (&acc)[NC], bool& bad, int hl, int kmax) {
+        if (!BOUNDED || 8 * KB < kmax) factor8<FWD>(a, invd, acc, bad, hl, kmax, std::make_integer_sequence<int, 8>{});
+        if constexpr (8 * KB + 8 < N) RBlock<NC, T, KB + 1, BOUNDED>::template factor<FWD>(a, invd, acc, bad, hl, kmax);
     }
     static __device__ __forceinline__ void forward(const T (&a)[NC][N], const T (&invd)[NC], T (&acc)[NC], int hl, int kmax) {
         if (!BOUNDED || 8 * KB < kmax) forward8(a, invd, acc, hl, kmax, std::make_integer_sequence<int, 8>{});

@@ -250,6 +250,12 @@ class Context:
     def synchronize(self):
         check(lib.fx_ctx_synchronize(self._h), "fx_ctx_synchronize")
 
+    def plan_bytes(self) -> int:
+        """Diagnostic: device bytes the context's cached sparse-path plans hold beyond their value slabs (fx_debug_ctx_plan_bytes)."""
+        b = C.c_uint64(0)
+        check(lib.fx_debug_ctx_plan_bytes(self._h, C.byref(b)), "fx_debug_ctx_plan_bytes")
+        return int(b.value)
+
     def timer_begin(self):
         check(lib.fx_timer_begin(self._h), "fx_timer_begin")
 

@@ -571,6 +571,17 @@ int fx_debug_grouped_build(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* op
 }
 FX_CATCH_CODE
 
+int fx_debug_ctx_plan_bytes(fx_ctx* ctx, uint64_t* bytes) try {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!bytes) return fail(FX_ERR_INVALID, "bad argument");
+    uint64_t t = 0;
+    for (const fx_ctx::PlanEntry& e : ctx->plan_cache) t += fx::sparse_cache_device_bytes(e.plan);
+    *bytes = t;
+    return FX_OK;
+}
+FX_CATCH_CODE
+
 // Diagnostic (not part of the drop-in surface): runs the stamped build of the fused kernel once and
 // returns the shader cycles summed over all wavefronts for {setup, eval, form, factor, solve, tail}.
 int fx_debug_phase_cycles(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, uint64_t cycles[6]) try {

@@ -49,6 +49,7 @@ SparsePlanCache* sparse_cache_new() { return nullptr; }
 void sparse_cache_free(SparsePlanCache*) {}
 bool sparse_cache_ready(const SparsePlanCache*) { return false; }
 void sparse_cache_keep_slab(SparsePlanCache*, size_t) {}
+size_t sparse_cache_device_bytes(const SparsePlanCache*) { return 0; }
 hipError_t sparse_solve_group(const fx_batch*, const DeviceBatch&, const uint32_t*, uint32_t, const LmParams&, hipStream_t, SparsePlanCache*, bool) {
     return hipErrorNoDevice;
 }

@@ -360,6 +360,12 @@ struct Arena {
         for (const Chunk& c : chunks) t += c.size;
         return t;
     }
+    // where the mark stands: every byte handed out so far, chunk tails skipped over included (a chunk's size would hide growth)
+    size_t taken() const {
+        size_t t = cur < chunks.size() ? used : 0;
+        for (size_t i = 0; i < cur && i < chunks.size(); ++i) t += chunks[i].size;
+        return t;
+    }
     // nothing of the arena is in use (the stream is synced, every Pool has ended): memory beyond `keep` goes back to the driver
     void trim(size_t keep) {
         if (bytes() <= keep) return;
@@ -438,14 +444,22 @@ struct SparsePlanCache {
     std::vector<std::unique_ptr<BlockOnDevice>> blocks;  // in visiting order
     uint32_t max_m = 0, max_nv = 0, max_nnz_j = 0, max_nnz_a = 0, max_nnz_l = 0, max_fslots = 0, max_bslots = 0;
     uint32_t max_mf_l = 0, max_mf_gu = 0;            // the multifrontal build's global storage (fx_front.h)
-    // a resident batch's group (sparse_cache_keep_slab(SIZE_MAX)): where its Systems sit in the batch's arrays, on the device — the
-    // same every solve, so uploaded once (the host copy stays for as long as the copy may be in flight)
+    // [vars0 offset | parameter offset | System id] of the group's Systems as the last solve that kept them uploaded them
+    // (sparse_solve_group, stay_async), and the Systems' indices. A later solve passes d_off on only if it would upload
+    // exactly off_host: a resident batch's group (sparse_cache_keep_slab(SIZE_MAX)) by the index list, as its offsets never
+    // change; a context's own plan by the table itself, as one-shot calls place the structure behind Systems of any size.
+    // One buffer of off_cap entries, reused while big enough and replaced (hipFree) when not: the memory stays bounded
+    // however often the layout changes. The host copy stays for as long as the copy may be in flight.
     std::vector<uint32_t> off_systems;
     std::vector<uint64_t> off_host;
     uint64_t* d_off = nullptr;
+    size_t off_cap = 0;
     Arena values;                                    // the group solves' value slabs, kept between calls (one solve at a time)
     size_t keep_values = size_t(256) << 20;          // ... up to this many bytes (sparse_cache_keep_slab)
     bool ready = false;
+    ~SparsePlanCache() {
+        if (d_off) (void)hipFree(d_off);
+    }
 };
 SparsePlanCache* sparse_cache_new() { return new SparsePlanCache(); }
 void sparse_cache_keep_slab(SparsePlanCache* c, size_t bytes) {
@@ -453,6 +467,7 @@ void sparse_cache_keep_slab(SparsePlanCache* c, size_t bytes) {
 }
 void sparse_cache_free(SparsePlanCache* c) { delete c; }
 bool sparse_cache_ready(const SparsePlanCache* c) { return c && c->ready; }
+size_t sparse_cache_device_bytes(const SparsePlanCache* c) { return c ? c->arena.taken() + c->off_cap * sizeof(uint64_t) : 0; }
 
 namespace {
 
@@ -939,32 +954,59 @@ hipError_t sparse_solve_group(const fx_batch* b, const DeviceBatch& d, const uin
             (void)hipMemsetAsync(Ld.rk, 0, (size_t)n * MF_MAX_RANKS * sizeof(MfRank), stream);
             (void)hipMemsetAsync(Ld.tickets, 0, (size_t)n * (2 * MF_MAX_RANKS + 2) * sizeof(uint32_t), stream);
         }
-        // [out / vars0 offset | parameter offset | system id] per System. A resident batch's group, solved whole: uploaded once and kept
-        // with the plan — such a solve then has nothing of the host's in flight and nothing to give back, and ends without a wait
-        // (stay_async: the caller's next work is on this stream too)
-        // (a context's own plan — one-shot calls — as well, as long as its slab stays under the bound it may keep: trimming needs the wait)
+        // [out / vars0 offset | parameter offset | system id] per System. A group solved whole on a plan that is kept (a resident batch's,
+        // or the context's own for one-shot calls, as long as its slab stays under the bound it may keep: trimming needs the wait): the
+        // table stays with the plan, and a later solve that would upload the same table uses it as it is — such a solve then has nothing
+        // of the host's in flight and nothing to give back, and ends without a wait (stay_async: the caller's next work is on this
+        // stream too). The same table: a resident batch's offsets never change, so its index list decides; a context's plan serves
+        // one-shot calls that put the structure behind Systems of any size, so the table itself is compared (n entries).
         const bool keep_off = stay_async && n == n_sys && cache->values.bytes() <= cache->keep_values && !team_prof && !trace;
-        bool off_cached = keep_off && cache->d_off && cache->off_systems.size() == n && std::equal(systems, systems + n, cache->off_systems.begin());
+        const bool resident_plan = cache->keep_values == SIZE_MAX;
         std::vector<uint64_t> h_off;
-        uint64_t* d_off = nullptr;
-        if (off_cached) {
-            d_off = cache->d_off;
-        } else {
+        auto fill_off = [&] {
             h_off.resize(3 * (size_t)n);
             for (uint32_t k = 0; k < n; ++k) {
                 h_off[k] = b->var_off[systems[g0 + k]];
                 h_off[n + k] = b->expr_off[systems[g0 + k]];
                 h_off[2 * (size_t)n + k] = systems[g0 + k];
             }
+        };
+        bool off_cached = false;
+        if (keep_off && cache->d_off) {
+            if (resident_plan) {
+                off_cached = cache->off_systems.size() == n && std::equal(systems, systems + n, cache->off_systems.begin());
+            } else {
+                fill_off();
+                off_cached = h_off == cache->off_host;
+            }
+        }
+        uint64_t* d_off = nullptr;
+        if (off_cached) {
+            d_off = cache->d_off;
+        } else {
+            if (h_off.empty()) fill_off();
             if (keep_off) {  // (this solve still waits at its end: the next one finds the copy done)
                 hipError_t e2 = hipSuccess;
                 cache->off_systems.clear();
-                cache->d_off = static_cast<uint64_t*>(cache->arena.take(h_off.size() * sizeof(uint64_t), e2));
-                if (!cache->d_off) return e2;
+                cache->off_host.clear();
+                if (cache->off_cap < h_off.size()) {  // (an earlier solve may still read the old table: the stream first)
+                    if (cache->d_off) {
+                        e2 = hipStreamSynchronize(stream);
+                        (void)hipFree(cache->d_off);
+                        cache->d_off = nullptr;
+                        cache->off_cap = 0;
+                        if (e2 != hipSuccess) return e2;
+                    }
+                    void* p = nullptr;
+                    e2 = hipMalloc(&p, h_off.size() * sizeof(uint64_t));
+                    if (e2 != hipSuccess) return e2;
+                    cache->d_off = static_cast<uint64_t*>(p);
+                    cache->off_cap = h_off.size();
+                }
                 cache->off_host = h_off;
                 e2 = hipMemcpyAsync(cache->d_off, cache->off_host.data(), h_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
                 if (e2 != hipSuccess) {
-                    cache->d_off = nullptr;
+                    cache->off_host.clear();
                     return e2;
                 }
                 cache->off_systems.assign(systems, systems + n);

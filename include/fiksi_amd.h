@@ -367,6 +367,10 @@ int fx_debug_solve_route(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts
  * fx_ctx_set_one_structure_builds(ctx, 2) keeps such batches on build 1). A context created under FIKSI_AMD_GROUPED_C=0 takes
  * none of 1, 2, 3, 4. Launches nothing. */
 int fx_debug_grouped_build(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, int* build);
+/* Diagnostic only: device bytes the context's cached sparse-path plans (those of one-shot calls, fx_system_solve_batch) hold beyond
+ * their value slabs: what their index arenas have handed out up to the mark, plus their offset tables' buffers. The same after
+ * any number of calls on structures the cache already holds, wherever in the batch they sit. Launches nothing, waits for nothing. */
+int fx_debug_ctx_plan_bytes(fx_ctx* ctx, uint64_t* bytes);
 
 /* ---- host-buffer entry points (upload -> run -> download; PCIe inclusive) ------------------- */
 /* == assemble::solve: batch->vars in: unscaled values, out: solved values. results may be NULL.

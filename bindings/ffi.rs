@@ -132,6 +132,8 @@ extern "C" {
     pub fn fx_debug_phase_cycles(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, cycles: *mut u64) -> c_int;
     pub fn fx_debug_solve_route(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, route: *mut c_int) -> c_int;
     pub fn fx_debug_grouped_build(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, build: *mut c_int) -> c_int;
+    pub fn fx_debug_grouped_factor(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, band: *mut c_int) -> c_int;
+    pub fn fx_gc_factor_profile(batch: *const fx_batch, system: u32, n: *mut u32, first: *mut u8, band: *mut c_int) -> c_int;
     pub fn fx_debug_ctx_plan_bytes(ctx: *mut fx_ctx, bytes: *mut u64) -> c_int;
     pub fn fx_system_solve_batch(ctx: *mut fx_ctx, batch: *const fx_batch, opts: *const fx_solving_opts, results: *mut fx_result) -> c_int;
     pub fn fx_host_register(ctx: *mut fx_ctx, ptr: *mut c_void, bytes: usize) -> c_int;

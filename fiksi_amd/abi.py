@@ -133,6 +133,19 @@ def single_pass_blocks(arrays, system: int = 0):
             for k in range(nb.value)]
 
 
+def gc_factor_profile(arrays, system: int = 0):
+    """The row profile of the Cholesky factor of System ``system`` (one component) in the column order of the one-structure
+    build's program, and the factor build its two-column kernel takes (host-side, no GPU needed): (first, band), first[i] = row
+    i's first structural non-zero column, fill included, over 16, 32 or 48 rows; band 0 = dense (fx_gc_factor_profile)."""
+    a = normalize_batch(arrays)
+    st = as_struct(a)
+    n = C.c_uint32(0)
+    band = C.c_int(0)
+    first = np.zeros(48, dtype=np.uint8)
+    check(lib.fx_gc_factor_profile(C.byref(st), system, C.byref(n), _ptr(first), C.byref(band)), "fx_gc_factor_profile")
+    return first[:n.value].astype(int).tolist(), int(band.value)
+
+
 def atan2_cr(y, x) -> np.ndarray:
     """The correctly rounded atan2 of the FX_STEP_QR kernels, host build (element-wise; no GPU needed)."""
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -399,6 +412,14 @@ class DeviceBatch:
         o = opts if opts is not None else solving_opts()
         r = C.c_int(0)
         check(lib.fx_debug_grouped_build(self.ctx.handle, self._h, C.byref(o), C.byref(r)), "fx_debug_grouped_build")
+        return int(r.value)
+
+    def grouped_factor(self, opts=None) -> int:
+        """The factor of build 1's two-column f64 kernel: 0 dense, k > 0 the band build k (GC_BANDS[k - 1] of fx_device.h),
+        -1: the solve does not run that kernel (diagnostic; fx_debug_grouped_factor)."""
+        o = opts if opts is not None else solving_opts()
+        r = C.c_int(0)
+        check(lib.fx_debug_grouped_factor(self.ctx.handle, self._h, C.byref(o), C.byref(r)), "fx_debug_grouped_factor")
         return int(r.value)
 
     def schedule_by_last_solve(self, enable: bool = True):

@@ -74,6 +74,15 @@ template <int NC, int RC> struct GcTable {  // NC columns per lane, RC chunks of
                               PE = LT + 16 * NC * NV;
 };
 
+// The band-factor instantiations of the one-structure build's two-column f64 kernel (fx_grouped_band.hip; fx_grouped_rows.h:
+// RBand): a factor whose rows lie within half-width w of the diagonal, except the last b rows, which are dense. Cheapest first
+// (multiply-adds of the factor: 220, 378, 451 against the dense 856). A program's band is 1 + its index here; 0: the dense factor.
+struct GcBand {
+    int w, b;
+};
+constexpr GcBand GC_BANDS[] = {{5, 0}, {5, 4}, {5, 6}};
+constexpr uint32_t GC_NBANDS = sizeof(GC_BANDS) / sizeof(GC_BANDS[0]);
+
 // One structure class of a batch of several structures, for a launch of fx_grouped_c.hip over the batch's big classes: its program
 // (words into gc_tab), its members (entries into order)
 struct GcClass {
@@ -152,6 +161,7 @@ struct DeviceBatch {
     uint32_t gc_rc;                       // ... and its chunks of 16 expressions: gc_nc, or twice that for an over-constrained structure
     const GcClass* gc_classes;            // a launch over several structure classes (null: one program, the whole batch)
     uint32_t gc_nclasses;
+    uint32_t gc_band;                     // the two-column program's factor: 1 + its GC_BANDS entry, 0 = dense (build_gc_program)
     // the program of its sparse build (fx_grouped_s.hip; build_gs_program): uniform batches with one component of 33 ... 255 free
     // variables (33 ... 48: a factor of at most a quarter of the dense triangle), at most 255 variables / expressions, a Cholesky
     // factor of at most 1023 slots and at most 1023 compact Jacobian entries; null otherwise
@@ -182,6 +192,7 @@ struct LmParams {
     // 1 = whenever the batch qualifies; the size from which a batch takes it
     int route_grouped = -1;
     int grouped_one_structure = 1;  // 0: batches of one structure stay on the general build (fx_grouped_c.hip is never taken)
+    int gc_band = 1;                // 0: the one-structure build factors densely even where its program names a band build
     uint32_t grouped_min_systems = 8u;
     uint32_t hold_passes = 2u;  // grouped kernel: passes a finished row waits for a second one before its set-up blocks (fx_ctx_set_hold_passes)
     // grouped kernel, the lambda ladder (fx_ctx_set_ladder): rows without a System of their own try the next lambdas of a
@@ -231,6 +242,7 @@ size_t grouped_lds_bytes(const DeviceBatch& b, uint32_t element_size, bool singl
 // ... its build for batches of one structure, two wavefronts per SIMD (fx_grouped_c.hip)
 bool grouped_c_applies(const DeviceBatch& b, const LmParams& p);
 hipError_t launch_solve_grouped_c(const DeviceBatch& b, const LmParams& p, hipStream_t stream);
+int grouped_c_band(const DeviceBatch& b, const LmParams& p);  // the factor of its two-column f64 launch: 1 + GC_BANDS entry, 0 = dense, -1 = no such launch
 size_t grouped_c_lds_bytes(const DeviceBatch& b, uint32_t element_size);
 // ... and its sparse build for batches of one structure of 33 ... 255 free variables with a small factor (fx_grouped_s.hip)
 bool grouped_s_applies(const DeviceBatch& b, const LmParams& p);

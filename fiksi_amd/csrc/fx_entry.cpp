@@ -93,6 +93,8 @@ int fx_ctx_create(fx_ctx** out, int device) try {
     ctx->device = device;
     if (const char* sw = getenv("FIKSI_AMD_GROUPED_C"))  // A / B and tests: 0 keeps every batch on the grouped kernel's general build
         if (sw[0] == '0') ctx->grouped_one_structure = 0;
+    if (const char* sw = getenv("FIKSI_AMD_GC_BAND"))  // A / B and tests: 0 keeps the one-structure build on its dense factor
+        if (sw[0] == '0') ctx->gc_band = 0;
     if (const char* sw = getenv("FIKSI_AMD_GROUPED")) {  // the default of fx_ctx_set_routing's first option
         if (sw[0] == '0') ctx->route_grouped = 0;
         if (sw[0] == '1') ctx->route_grouped = 1;
@@ -567,6 +569,46 @@ int fx_debug_grouped_build(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* op
         if (fx::grouped_c_applies(dc, p)) *build = 3;
     }
     if (*build == 1 && fx::grouped_tiny_applies(db->d, p)) *build = 4;
+    return FX_OK;
+}
+FX_CATCH_CODE
+
+int fx_debug_grouped_factor(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, int* band) try {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!db || !band) return fail(FX_ERR_INVALID, "bad argument");
+    int build = 0;
+    rc = fx_debug_grouped_build(ctx, db, opts, &build);
+    if (rc) return rc;
+    fx_solving_opts o;
+    if (opts) o = *opts; else fx_solving_opts_default(&o);
+    fx::LmParams p;
+    ctx->route(p);
+    p.lm = o.lm;
+    p.mode = 1u | (o.perturb ? 2u : 0u) | (o.optimizer == 1 ? fx::MODE_LBFGS : 0u) | (o.decomposer == 1 ? fx::MODE_UNITS : 0u);
+    *band = build == 1 ? fx::grouped_c_band(db->d, p) : -1;
+    return FX_OK;
+}
+FX_CATCH_CODE
+
+int fx_gc_factor_profile(const fx_batch* batch, uint32_t system, uint32_t* n, uint8_t* first, int* band) try {
+    if (!n || !first || !band) return fail(FX_ERR_INVALID, "bad argument");
+    HostPlan p;
+    int rc = analyze(batch, &p);
+    if (rc) return rc;
+    if (system >= batch->n_systems) return fail(FX_ERR_INVALID, "system %u out of range (%u systems)", system, batch->n_systems);
+    const uint32_t v0 = batch->var_off[system], nvt = batch->var_off[system + 1] - v0;
+    const uint32_t e0 = batch->expr_off[system], net = batch->expr_off[system + 1] - e0;
+    uint32_t nfree = 0;
+    for (uint32_t i = 0; i < nvt; ++i) nfree += batch->var_fixed[v0 + i] ? 0u : 1u;
+    GcHostProgram gc;
+    if (nfree == 0 || nfree > 48u ||
+        !build_gc_program(p.var_info.data() + v0, p.expr_tagx.data() + e0, p.expr_comp.data() + e0, p.expr_idx16.data() + 4 * (size_t)e0, nvt,
+                              net, nfree, gc))
+        return fail(FX_ERR_INVALID, "system %u has no program of the one-structure build (one component of 1 ... 48 free variables)", system);
+    *n = 16u * gc.nc;
+    memcpy(first, gc.first, *n);
+    *band = (int)gc.band;
     return FX_OK;
 }
 FX_CATCH_CODE

@@ -75,11 +75,30 @@ __device__ __forceinline__ void seq_add(double& sum, double t) { seq_add_impl(su
 // ------------------------------------------------------------------------------------------
 // Cholesky of fx_chol.h with the columns of one matrix spread over a row: lane r holds column r + 16 q in
 // a[q][.] (same operations on the same operands as chol_factor / chol_solve: bit-identical results)
+//
+// W, B: a factor whose row profile lies inside a band of half-width W plus a dense border of the last B rows (row i's first
+// non-zero column, fill included, is at least i - W unless i >= N - B; the host checks it for the structure, fx_programs.cpp).
+// Factor step K then updates only the rows i with i - K <= W or i >= N - B: the others hold an exact +0 in column K, and
+// a - (+-0) * mul is a for every a that is not -0 (a sum that starts from +0 never is) and every finite mul. The default
+// (W = N) is the dense factor.
 // ------------------------------------------------------------------------------------------
-template <int NC, typename T, int K, bool BOUNDED>
+template <int NC, int W, int B>
+struct RBand {
+    static constexpr int N = RS * NC;
+    static constexpr bool SKIPS = W + 1 < N - B;  // some update of the dense factor is left out
+    static constexpr bool updates(int i, int k) { return i - k <= W || i >= N - B; }
+    // no lane of array q holds a non-zero of row i: every (i, j), j = 16 q ... 16 q + 15, lies outside the envelope
+    static constexpr bool zero_row(int q, int i) {
+        for (int j = RS * q; j < RS * q + RS; ++j)
+            if (updates(i > j ? i : j, i > j ? j : i)) return false;
+        return true;
+    }
+};
+template <int NC, typename T, int K, bool BOUNDED, int W = RS * NC, int B = 0>
 struct RStep {  // one column step of the factorization / of a triangular solve
     static constexpr int N = RS * NC;
     static constexpr int KA = K / RS, KL = K % RS;  // array and lane of column K
+    using Band = RBand<NC, W, B>;
     // FWD: forward substitution step K right behind factor step K (`forward` below, the same operations on the same
     // operands: what it reads — a[.][K] of the lanes above K and invd of lane K, which is rs — is final once factor step K
     // is done, and no later factor step writes it)
@@ -90,6 +109,9 @@ struct RStep {  // one column step of the factorization / of a triangular solve
         bad = bad || !(piv > T(0)) || !(piv < Lim<T>::huge());
         const T rs = rsqrt_refined(piv);
         const T ip = rs * rs;  // 1/pivot
+        // a band factor: 1/pivot overflows on a denormal pivot, and then the dense factor's next pivot is NaN or -inf (it
+        // updates row K + 1 with mul = inf or 0 * inf); the band factor may skip that update, so it says `bad` here
+        if constexpr (Band::SKIPS && K < N - 1) bad = bad || !(ip < Lim<T>::huge());
         T mul[NC];
 #pragma unroll
         for (int q = 0; q < NC; ++q) {
@@ -107,6 +129,7 @@ struct RStep {  // one column step of the factorization / of a triangular solve
         if constexpr (NC <= 2) {
 #pragma unroll
             for (int i = K + 1; i < N; ++i) {
+                if (!Band::updates(i, K)) continue;  // L(i, K) is a structural zero
 #pragma unroll
                 for (int q = NC - 1; q >= KA; --q) {
                     if (q == KA && KL == RS - 1) continue;  // no column of this array lies above K
@@ -132,6 +155,7 @@ struct RStep {  // one column step of the factorization / of a triangular solve
                 }
             }
             static_assert(!FWD, "the 48-column build substitutes in a pass of its own");
+            static_assert(!Band::SKIPS, "the 48-column build factors densely");
         }
         }
     }
@@ -190,12 +214,12 @@ struct RStep {  // one column step of the factorization / of a triangular solve
 // variables are identity padding that no other column depends on, so a block of steps at or past kmax is skipped.
 // (One test per eight steps, and none in the other builds: the scheduler needs long straight-line regions here —
 // a test per step cost the headline shape 25 %.)
-template <int NC, typename T, int KB, bool BOUNDED>
+template <int NC, typename T, int KB, bool BOUNDED, int W = RS * NC, int B = 0>
 struct RBlock {
     static constexpr int N = RS * NC;
     template <bool FWD, int... I>
     static __device__ __forceinline__ void factor8(T (&a)[NC][N], T (&invd)[NC], T (&acc)[NC], bool& bad, int hl, int kmax, std::integer_sequence<int, I...>) {
-        (RStep<NC, T, 8 * KB + I, BOUNDED>::template factor<FWD>(a, invd, acc, bad, hl, kmax), ...);
+        (RStep<NC, T, 8 * KB + I, BOUNDED, W, B>::template factor<FWD>(a, invd, acc, bad, hl, kmax), ...);
     }
     template <int... I>
     static __device__ __forceinline__ void forward8(const T (&a)[NC][N], const T (&invd)[NC], T (&acc)[NC], int hl, int kmax, std::integer_sequence<int, I...>) {
@@ -210,7 +234,7 @@ struct RBlock {
     template <bool FWD>
     static __device__ __forceinline__ void factor(T (&a)[NC][N], T (&invd)[NC], T (&acc)[NC], bool& bad, int hl, int kmax) {
         if (!BOUNDED || 8 * KB < kmax) factor8<FWD>(a, invd, acc, bad, hl, kmax, std::make_integer_sequence<int, 8>{});
-        if constexpr (8 * KB + 8 < N) RBlock<NC, T, KB + 1, BOUNDED>::template factor<FWD>(a, invd, acc, bad, hl, kmax);
+        if constexpr (8 * KB + 8 < N) RBlock<NC, T, KB + 1, BOUNDED, W, B>::template factor<FWD>(a, invd, acc, bad, hl, kmax);
     }
     static __device__ __forceinline__ void forward(const T (&a)[NC][N], const T (&invd)[NC], T (&acc)[NC], int hl, int kmax) {
         if (!BOUNDED || 8 * KB < kmax) forward8(a, invd, acc, hl, kmax, std::make_integer_sequence<int, 8>{});

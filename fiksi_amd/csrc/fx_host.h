@@ -153,6 +153,7 @@ struct fx_ctx {
     // routing of batches of small Systems (fx_ctx_set_routing)
     int route_grouped = -1;
     int grouped_one_structure = 1;  // the grouped kernel's build for batches of one structure (FIKSI_AMD_GROUPED_C=0: never)
+    int gc_band = 1;                // ... its band-factor instantiations (FIKSI_AMD_GC_BAND=0: the dense factor always)
     uint32_t grouped_min_systems = 8u;
     int presort = 1;                       // fx_ctx_set_presort
     uint32_t hold_passes = 2u;             // fx_ctx_set_hold_passes
@@ -241,6 +242,7 @@ struct fx_ctx {
     void route(fx::LmParams& p) const {
         p.route_grouped = route_grouped;
         p.grouped_one_structure = grouped_one_structure;
+        p.gc_band = gc_band;
         p.grouped_min_systems = grouped_min_systems;
         p.hold_passes = hold_passes;
         p.ladder = ladder;
@@ -440,6 +442,8 @@ struct QrHostPlan {
 struct GcHostProgram {
     std::vector<uint32_t> words;
     uint32_t nslots = 0, ng = 0, nc = 0, rc = 0, words_f64 = 0;  // (words_f64: the part the f64 builds use)
+    uint32_t band = 0;  // two columns per lane: 1 + the GC_BANDS entry whose band and border hold the factor's rows, 0 = none does
+    uint8_t first[48] = {0};  // the factor's row profile in the kernel's column order: row i's first non-zero column (16 nc rows)
 };
 struct GsHostProgram {
     std::vector<uint32_t> words;

@@ -77,6 +77,33 @@ bool build_qr_plan(const uint8_t* expr_tag, const uint16_t* expr_idx16, const ui
     return true;
 }
 
+// The row profile of the Cholesky factor of a pattern (lower[k]: the rows below k where column k of Jt J is a structural
+// non-zero): first[i] = row i's first non-zero column, fill included. The symbolic factorization by the elimination tree: column
+// k's rows join the column of its first off-diagonal row.
+static void factor_profile(uint64_t (&lower)[48], uint32_t n, uint8_t (&first)[48]) {
+    for (uint32_t i = 0; i < n; ++i) first[i] = (uint8_t)i;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (!lower[k]) continue;
+        const uint32_t p = (uint32_t)__builtin_ctzll(lower[k]);
+        lower[p] |= lower[k] & ~(1ull << p);
+        for (uint64_t m = lower[k]; m; m &= m - 1u) {
+            const uint32_t i = (uint32_t)__builtin_ctzll(m);
+            if (k < first[i]) first[i] = (uint8_t)k;
+        }
+    }
+}
+// The cheapest band-factor build of the two-column kernel (fx_device.h: GC_BANDS) whose band and border hold every row of the
+// profile: 1 + its entry, 0 if none does (the dense factor)
+static uint32_t gc_band_for(const uint8_t (&first)[48], uint32_t n) {
+    for (uint32_t t = 0; t < fx::GC_NBANDS; ++t) {
+        const int w = fx::GC_BANDS[t].w, b = fx::GC_BANDS[t].b;
+        bool holds = true;
+        for (int i = 0; i < (int)n - b; ++i) holds = holds && i - (int)first[i] <= w;
+        if (holds) return t + 1u;
+    }
+    return 0u;
+}
+
 // The program of the grouped kernel's one-structure build (fx_grouped_c.hip): everything about a System's STRUCTURE that kernel
 // needs, written once for a batch whose Systems all share it — one component, at most NV = 32 (48) variables and expressions
 // (every expression a row of the component), 17 ... 32 (33 ... 48) free variables: two (three) matrix columns per lane. Jt J is kept by its pattern: a slot per structural non-zero of
@@ -148,6 +175,14 @@ static bool build_gc_program_t(const uint16_t* var_info, const uint8_t* expr_tag
     const uint32_t zero = nslots++;
     nslots = (nslots + 3u) & ~3u;  // (whole 16-byte vectors in f32 too)
     if (nslots > 256u) return false;
+    {  // the factor's row profile in the kernel's column order (the identity padding past the free variables: diagonal only)
+        uint64_t lower[48] = {0};
+        for (uint32_t i = 0; i < NV; ++i)
+            for (uint32_t k = 0; k < i; ++k)
+                if (slot_of[tri(i, k)] >= 0) lower[k] |= 1ull << i;
+        factor_profile(lower, NV, out.first);
+        if (NC == 2 && RC == 2) out.band = gc_band_for(out.first, NV);
+    }
     std::vector<uint32_t> pw, pe;
     for (uint32_t r = 0; r < net; ++r)
         for (int a = 0; a < 8; ++a) {

@@ -837,6 +837,7 @@ int upload_planned(fx_ctx* ctx, const fx_batch* batch, const HostPlan& p, uint32
         d.gc_ng = gc.ng;
         d.gc_nc = gc.nc;
         d.gc_rc = gc.rc;
+        d.gc_band = gc.band;
     }
     // Several structures: the classes with 2 048 members and more (at most eight, the largest first; those of the largest one's
     // build — columns per lane) get a program each

@@ -367,6 +367,16 @@ int fx_debug_solve_route(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts
  * fx_ctx_set_one_structure_builds(ctx, 2) keeps such batches on build 1). A context created under FIKSI_AMD_GROUPED_C=0 takes
  * none of 1, 2, 3, 4. Launches nothing. */
 int fx_debug_grouped_build(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, int* build);
+/* Diagnostic only: the Cholesky factor of build 1's two-column f64 kernel (17 ... 32 free variables) for such a launch: 0 = the
+ * dense factor, k > 0 = the band build k, compiled for a factor whose rows lie within a fixed half-band of the diagonal except a
+ * few dense last rows (the structure's factor fits it; same bits), -1 = the launch is not that kernel. A context created under
+ * FIKSI_AMD_GC_BAND=0 takes the dense factor always. Launches nothing. */
+int fx_debug_grouped_factor(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, int* band);
+/* Host only, no device needed: the Cholesky factor of the normal matrix of System `system`, taken as one component, in the column
+ * order of build 1's program (its free variables ascending, then identity padding up to *n = 16, 32 or 48 columns): first[i] =
+ * row i's first structural non-zero column, fill included (first holds 48 bytes); *band = the factor build that launch takes as
+ * fx_debug_grouped_factor numbers them (0: dense). FX_ERR_INVALID if the System has no such program. */
+int fx_gc_factor_profile(const fx_batch* batch, uint32_t system, uint32_t* n, uint8_t* first, int* band);
 /* Diagnostic only: device bytes the context's cached sparse-path plans (those of one-shot calls, fx_system_solve_batch) hold beyond
  * their value slabs: what their index arenas have handed out up to the mark, plus their offset tables' buffers. The same after
  * any number of calls on structures the cache already holds, wherever in the batch they sit. Launches nothing, waits for nothing. */

@@ -133,6 +133,7 @@ extern "C" {
     pub fn fx_debug_solve_route(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, route: *mut c_int) -> c_int;
     pub fn fx_debug_grouped_build(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, build: *mut c_int) -> c_int;
     pub fn fx_debug_grouped_factor(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, band: *mut c_int) -> c_int;
+    pub fn fx_debug_grouped_staged(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, staged: *mut c_int) -> c_int;
     pub fn fx_gc_factor_profile(batch: *const fx_batch, system: u32, n: *mut u32, first: *mut u8, band: *mut c_int) -> c_int;
     pub fn fx_debug_ctx_plan_bytes(ctx: *mut fx_ctx, bytes: *mut u64) -> c_int;
     pub fn fx_system_solve_batch(ctx: *mut fx_ctx, batch: *const fx_batch, opts: *const fx_solving_opts, results: *mut fx_result) -> c_int;

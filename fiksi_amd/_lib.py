@@ -139,6 +139,7 @@ SIGNATURES = [
     ("fx_debug_solve_route", C.c_int, [_vp, _vp, C.POINTER(FxSolvingOpts), C.POINTER(C.c_int)]),
     ("fx_debug_grouped_build", C.c_int, [_vp, _vp, C.POINTER(FxSolvingOpts), C.POINTER(C.c_int)]),
     ("fx_debug_grouped_factor", C.c_int, [_vp, _vp, C.POINTER(FxSolvingOpts), C.POINTER(C.c_int)]),
+    ("fx_debug_grouped_staged", C.c_int, [_vp, _vp, C.POINTER(FxSolvingOpts), C.POINTER(C.c_int)]),
     ("fx_gc_factor_profile", C.c_int, [C.POINTER(FxBatch), C.c_uint32, C.POINTER(C.c_uint32), _vp, C.POINTER(C.c_int)]),
     ("fx_debug_ctx_plan_bytes", C.c_int, [_vp, u64p]),
     ("fx_timer_begin", C.c_int, [_vp]),

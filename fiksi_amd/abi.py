@@ -422,6 +422,14 @@ class DeviceBatch:
         check(lib.fx_debug_grouped_factor(self.ctx.handle, self._h, C.byref(o), C.byref(r)), "fx_debug_grouped_factor")
         return int(r.value)
 
+    def grouped_staged(self, opts=None) -> int:
+        """1: build 1 or 3's two-column f64 kernel gets every System set up by a pass before it and checked by a pass after it,
+        0: the kernel does both itself, -1: the solve is neither build (diagnostic; fx_debug_grouped_staged)."""
+        o = opts if opts is not None else solving_opts()
+        r = C.c_int(0)
+        check(lib.fx_debug_grouped_staged(self.ctx.handle, self._h, C.byref(o), C.byref(r)), "fx_debug_grouped_staged")
+        return int(r.value)
+
     def schedule_by_last_solve(self, enable: bool = True):
         """Later solves start the Systems that took the most LM trials in the last solve first (results unchanged)."""
         check(lib.fx_batch_schedule_by_last_solve(self.ctx.handle, self._h, 1 if enable else 0), "fx_batch_schedule_by_last_solve")

@@ -182,6 +182,15 @@ struct DeviceBatch {
     const double* param_in;    // [n_exprs] ... of the caller's expr_param
     double* vars_out;          // [n_vars] ... of the caller's vars again (written: free variables of a finished System)
     fx_result* results_out;    // [n_systems] ... of the caller's results
+    // The staged set-up of the one-structure build's two-column f64 kernel (fx_grouped_c.hip: gc_stage_kernel, gc_close_kernel): what
+    // the kernel's NEXT phase computed per System — its scale, its scaled and perturbed start point, its scaled parameters — written
+    // by a streaming pass before the solve, 16 lanes per System, at the System's place j in the launch's hand-out list (`order`, or
+    // the System numbers when there is none), so that a ticket leads to its data without the list look-up in between; the closing
+    // check is a pass after it. Null: the kernel does both itself.
+    double* st_x;      // [n_systems][32]
+    double* st_p;      // [n_systems][32]
+    double* st_scale;  // [n_systems]
+    uint32_t* st_sys;  // [n_systems] the System at place j
 };
 
 struct LmParams {
@@ -193,8 +202,10 @@ struct LmParams {
     int route_grouped = -1;
     int grouped_one_structure = 1;  // 0: batches of one structure stay on the general build (fx_grouped_c.hip is never taken)
     int gc_band = 1;                // 0: the one-structure build factors densely even where its program names a band build
+    int gc_staged = 1;              // 0: the one-structure build sets up and checks every System inside the solve (DeviceBatch::st_x)
     uint32_t grouped_min_systems = 8u;
     uint32_t hold_passes = 2u;  // grouped kernel: passes a finished row waits for a second one before its set-up blocks (fx_ctx_set_hold_passes)
+    int hold_set = 0;           // ... set by the caller: a staged launch holds too (else it does not: fx_grouped_c.hip, the launcher)
     // grouped kernel, the lambda ladder (fx_ctx_set_ladder): rows without a System of their own try the next lambdas of a
     // running System of their wavefront side by side. ladder_tail / ladder_k: with at most ladder_tail Systems left in the
     // queue, a wavefront that holds a System past ladder_k trials takes no further Systems (0: rows only help once the
@@ -243,6 +254,7 @@ size_t grouped_lds_bytes(const DeviceBatch& b, uint32_t element_size, bool singl
 bool grouped_c_applies(const DeviceBatch& b, const LmParams& p);
 hipError_t launch_solve_grouped_c(const DeviceBatch& b, const LmParams& p, hipStream_t stream);
 int grouped_c_band(const DeviceBatch& b, const LmParams& p);  // the factor of its two-column f64 launch: 1 + GC_BANDS entry, 0 = dense, -1 = no such launch
+int grouped_c_staged(const DeviceBatch& b, const LmParams& p);  // 1: its launch takes the staged set-up and closing check, 0: not, -1 = no such launch
 size_t grouped_c_lds_bytes(const DeviceBatch& b, uint32_t element_size);
 // ... and its sparse build for batches of one structure of 33 ... 255 free variables with a small factor (fx_grouped_s.hip)
 bool grouped_s_applies(const DeviceBatch& b, const LmParams& p);

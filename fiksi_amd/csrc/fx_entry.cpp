@@ -95,6 +95,8 @@ int fx_ctx_create(fx_ctx** out, int device) try {
         if (sw[0] == '0') ctx->grouped_one_structure = 0;
     if (const char* sw = getenv("FIKSI_AMD_GC_BAND"))  // A / B and tests: 0 keeps the one-structure build on its dense factor
         if (sw[0] == '0') ctx->gc_band = 0;
+    if (const char* sw = getenv("FIKSI_AMD_GC_STAGED"))  // A / B and tests: 0 keeps every System's set-up and closing check in the solve kernel
+        if (sw[0] == '0') ctx->gc_staged = 0;
     if (const char* sw = getenv("FIKSI_AMD_GROUPED")) {  // the default of fx_ctx_set_routing's first option
         if (sw[0] == '0') ctx->route_grouped = 0;
         if (sw[0] == '1') ctx->route_grouped = 1;
@@ -155,6 +157,7 @@ FX_CATCH_CODE
 int fx_ctx_set_hold_passes(fx_ctx* ctx, uint32_t passes) try {
     if (!ctx) return fail(FX_ERR_INVALID, "ctx is NULL");
     ctx->hold_passes = passes;
+    ctx->hold_set = true;
     return FX_OK;
 }
 FX_CATCH_CODE
@@ -587,6 +590,31 @@ int fx_debug_grouped_factor(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* o
     p.lm = o.lm;
     p.mode = 1u | (o.perturb ? 2u : 0u) | (o.optimizer == 1 ? fx::MODE_LBFGS : 0u) | (o.decomposer == 1 ? fx::MODE_UNITS : 0u);
     *band = build == 1 ? fx::grouped_c_band(db->d, p) : -1;
+    return FX_OK;
+}
+FX_CATCH_CODE
+
+int fx_debug_grouped_staged(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, int* staged) try {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!db || !staged) return fail(FX_ERR_INVALID, "bad argument");
+    int build = 0;
+    rc = fx_debug_grouped_build(ctx, db, opts, &build);
+    if (rc) return rc;
+    fx_solving_opts o;
+    if (opts) o = *opts; else fx_solving_opts_default(&o);
+    fx::LmParams p;
+    ctx->route(p);
+    p.lm = o.lm;
+    p.mode = 1u | (o.perturb ? 2u : 0u) | (o.optimizer == 1 ? fx::MODE_LBFGS : 0u) | (o.decomposer == 1 ? fx::MODE_UNITS : 0u);
+    fx::DeviceBatch d = db->d;
+    if (!d.st_x && gc_stage_wanted(ctx, db)) d.st_x = d.st_p = d.st_scale = reinterpret_cast<double*>(16);  // (allocated on the first solve; never read here)
+    *staged = -1;
+    if (build == 1) {
+        *staged = fx::grouped_c_staged(d, p);
+    } else if (build == 3) {  // (the class launch's own batch: fx_solve.cpp, launch_class_solves)
+        *staged = (p.gc_staged && d.st_x && db->cl_nc == 2u && db->cl_rc == 2u && p.lm.precision != 32) ? 1 : 0;
+    }
     return FX_OK;
 }
 FX_CATCH_CODE

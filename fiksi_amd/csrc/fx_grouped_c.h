@@ -15,30 +15,93 @@ namespace fx {
 // A System's block, bytes: everything of fixed size first, at offsets the instructions carry as immediates (one base register per
 // row), then Jt J's slots and behind them the compact Jacobian rows
 // (NV = 16 NC: the most variables of a System in the build with NC columns per lane; NR = 16 RC: the most expressions — an
-// over-constrained structure takes the instantiation with twice the rows; ES: bytes of the compute type)
-template <int NV, int NR, int ES> struct GcBlock {
-    static constexpr uint32_t XS = 0, RHS = ES * NV, R = 2 * ES * NV, P = R + ES * NR, VOUT = P + ES * NR, STASH = VOUT + 8 * NV, A = STASH + 16;
+// over-constrained structure takes the instantiation with twice the rows; ES: bytes of the compute type; VO: 1 = the closing check's
+// unscaled values have a place, 0 = a staged build, whose closing check is a pass of its own)
+template <int NV, int NR, int ES, int VO = 1> struct GcBlock {
+    static constexpr uint32_t XS = 0, RHS = ES * NV, R = 2 * ES * NV, P = R + ES * NR, VOUT = P + ES * NR, STASH = VOUT + 8 * NV * VO, A = STASH + 16;
 };
 struct GcLayout {
     uint32_t tab_bytes, off_g, stride;
 };
 
-static GcLayout make_gc_layout(const DeviceBatch& b, uint32_t es) {
+static GcLayout make_gc_layout(const DeviceBatch& b, uint32_t es, bool staged = false) {
     GcLayout L;
     L.tab_bytes = ((es == 4u ? b.gc_words_all : b.gc_words) * 4u + 15u) & ~15u;
-    L.off_g = (2u * es + 8u) * 16u * b.gc_nc + 2u * es * 16u * b.gc_rc + 16u + b.gc_nslots * es;  // (slots are a multiple of four: 16-byte aligned)
+    L.off_g = (2u * es + (staged ? 0u : 8u)) * 16u * b.gc_nc + 2u * es * 16u * b.gc_rc + 16u + b.gc_nslots * es;  // (slots are a multiple of four: 16-byte aligned)
     L.stride = L.off_g + b.gc_ng * es;
     return L;
 }
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
-// W, B: the factor's band and border (fx_grouped_rows.h: RBand; the dense factor by default)
-template <int NC, int RC, typename T, int W = RS * NC, int B = 0>
+// sum over the expressions' chunks of a row's System, as wave_sum adds its blocks: (b0 + b1) + (b2 + b3)
+template <int RC, typename U>
+__device__ __forceinline__ U gc_rows_sum(const U (&part)[RC]) {
+    U s01 = row_sum(part[0]);
+    if constexpr (RC >= 2) s01 = s01 + row_sum(part[1]);
+    if constexpr (RC == 3) s01 = s01 + row_sum(part[2]);
+    if constexpr (RC == 4) s01 = s01 + (row_sum(part[2]) + row_sum(part[3]));
+    return s01;
+}
+
+// K0 of the System of a row of 16 lanes (assemble/mod.rs:32-44, 91-111): from its start values (c_var[k]: variable RS k + hl; colk:
+// its free column or -1) and its parameters (c_param[k], tagk[k]: expression RS k + hl), its scale — summed strictly in reference
+// order (utils.rs:11-33) — and, in f64, its scaled and perturbed start point x and its scaled parameters pe. Past nvt / net: zeros.
+// The kernel's own set-up and the staged one (gc_stage_kernel) both run this: the same operations in the same order.
+template <int NC, int RC>
+__device__ __forceinline__ double gc_setup(uint32_t mode, uint32_t nvt, uint32_t net, int hl, int gbase, const double (&c_var)[NC],
+                                           const int (&colk)[NC], const double (&c_param)[RC], const int (&tagk)[RC], double (&x)[NC],
+                                           double (&pe)[RC]) {
+    double scale = 1.0, scale_recip = 1.0;
+    if (mode & 1u) {
+        double sum = 0.0;
+        uint32_t count = nvt;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            if ((uint32_t)(RS * k) < nvt) seq_add(sum, c_var[k] * c_var[k]);  // (past the end: + 0.0, exact)
+#pragma unroll
+        for (int k = 0; k < RC; ++k) {
+            if ((uint32_t)(RS * k) < net) {
+                const bool isd = (uint32_t)(RS * k + hl) < net && (tagk[k] == FX_TAG_PPD || tagk[k] == FX_TAG_PLD);
+                count += (uint32_t)__popc((uint32_t)(__ballot(isd) >> gbase) & 0xFFFFu);
+                seq_add(sum, isd ? c_param[k] * c_param[k] : 0.0);
+            }
+        }
+        scale = ::sqrt(sum / (double)count);
+        scale_recip = 1.0 / scale;
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        x[k] = 0.0;
+        if ((uint32_t)(RS * k + hl) < nvt) {
+            double xx = (mode & 1u) ? c_var[k] * scale_recip : c_var[k];
+            if (colk[k] >= 0 && (mode & 2u)) {  // K0b: two draws of the LCG per free variable, in column order
+                uint32_t st = lcg_jump(42u, 2u * (uint32_t)colk[k]);
+                st = st * 1664525u + 1013904223u;
+                const double f1 = (1.0 / 4294967295.0) * (double)st;
+                st = st * 1664525u + 1013904223u;
+                const double f2 = (1.0 / 4294967295.0) * (double)st;
+                xx += xx * (1.0 / 8196.0) * f1 + (1.0 / 65568.0) * f2;
+            }
+            x[k] = xx;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < RC; ++k) {
+        pe[k] = c_param[k];
+        if ((mode & 1u) && (tagk[k] == FX_TAG_PPD || tagk[k] == FX_TAG_PLD)) pe[k] = scale_recip * c_param[k];
+    }
+    return scale;
+}
+
+// W, B: the factor's band and border (fx_grouped_rows.h: RBand; the dense factor by default). STAGED: every System's set-up comes
+// from b.st_x / st_p / st_scale and its closing check is left to gc_close_kernel (resident f64 batches; fx_grouped_c.hip: the launcher)
+template <int NC, int RC, typename T, int W = RS * NC, int B = 0, bool STAGED = false>
 __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmParams& prm, const GcLayout& L, uint32_t* __restrict__ next_system,
                                                unsigned char* smem) {
+    static_assert(!STAGED || (sizeof(T) == 8 && NC == 2 && RC == 2), "the staged set-up: f64, 32 + 32 values per place (fx_solve.cpp)");
     constexpr int N = RS * NC;
-    using BK = GcBlock<N, RS * RC, (int)sizeof(T)>;
+    using BK = GcBlock<N, RS * RC, (int)sizeof(T), STAGED ? 0 : 1>;
     using V16 = typename Vec16<T>::type;
     using TK = GcTable<NC, RC>;
     const int lane = threadIdx.x;
@@ -55,6 +118,7 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
     uint32_t qn = 0;                  // Systems in the queue
     const uint32_t* qlist = nullptr;  // ... their numbers (null: the ticket is the number)
     uint32_t* qhead = next_system;    // ... its head
+    uint32_t qbase = 0;               // ... where its list starts in b.order (the staged data of ticket t lie at place qbase + t)
     // (the tables of fixed size sit at fixed places: fx_device.h, GcTable)
     const int8_t* vcol = reinterpret_cast<const int8_t*>(smem + TK::VCOL);         // [N] variable -> free column or -1
     const uint8_t* fidx = smem + TK::FIDX;                                         // [N] free column -> variable
@@ -77,7 +141,6 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
     double* STASH = reinterpret_cast<double*>(base + BK::STASH);  // [2] the System's scale, the SSE of its start point
 
     const fx_lm_opts o = prm.lm;
-    auto gballot = [&](bool p) -> uint32_t { return (uint32_t)(__ballot(p) >> gbase) & 0xFFFFu; };
 
     // per lane, fixed for a program: the variables of its columns and the slots of their diagonal entries
     uint32_t my_vi[NC], dslot[NC];
@@ -121,13 +184,7 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
         return s01;
     };
     // ... over the expressions' chunks: (b0 + b1) + (b2 + b3)
-    auto rows_sum = [&](const auto (&part)[RC]) {
-        auto s01 = row_sum(part[0]);
-        if constexpr (RC >= 2) s01 = s01 + row_sum(part[1]);
-        if constexpr (RC == 3) s01 = s01 + row_sum(part[2]);
-        if constexpr (RC == 4) s01 = s01 + (row_sum(part[2]) + row_sum(part[3]));
-        return s01;
-    };
+    auto rows_sum = [&](const auto (&part)[RC]) { return gc_rows_sum<RC>(part); };
     // residuals and Jacobian rows of the point in XS
     auto eval_rows = [&]() -> T {
         T part[RC];
@@ -275,6 +332,7 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
             words = sizeof(T) == 4 ? k.words_all : k.words;
             qn = k.count;
             qlist = b.order + k.list_off;
+            qbase = k.list_off;
             qhead = next_system + c;
         }
         group_sync();
@@ -324,6 +382,8 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
                 if (tk >= qn) {
                     tk = 0xFFFFFFFFu;  // the queue is empty (a list — a schedule, or the members of a structure class — may hold
                                        // System numbers beyond the queue's length)
+                } else if (STAGED) {  // the place in the list (prm.spread is 0 without one): the staged data are there
+                    if (tk < 4u * prm.spread) tk = (tk & 3u) * prm.spread + (tk >> 2);
                 } else if (qlist) {
                     uint32_t pos = tk;
                     if (tk < 4u * prm.spread) pos = (tk & 3u) * prm.spread + (tk >> 2);
@@ -337,6 +397,17 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
                 qdone = true;
             } else {
                 s = nxt;
+                if constexpr (STAGED) {  // set up by gc_stage_kernel at the System's place in the list: one round trip for all of it
+                    const uint32_t j = qbase + nxt;
+                    s = b.st_sys[j];
+#pragma unroll
+                    for (int k = 0; k < NC; ++k)
+                        if ((uint32_t)(RS * k + hl) < nvt) XS[RS * k + hl] = b.st_x[(uint32_t)N * j + (uint32_t)(RS * k + hl)];
+#pragma unroll
+                    for (int k = 0; k < RC; ++k)
+                        if ((uint32_t)(RS * k + hl) < net) P[RS * k + hl] = b.st_p[(uint32_t)(RS * RC) * j + (uint32_t)(RS * k + hl)];
+                    if (hl == 0) STASH[0] = b.st_scale[j];
+                } else {
                 // (a launch over ONE structure class of a batch of several — b.uniform == 0 — reads the System's offsets)
                 const uint32_t v0 = b.uniform ? s * nvt : b.var_off[s], e0 = b.uniform ? s * net : b.expr_off[s];
                 double c_var[NC], c_param[RC];
@@ -364,53 +435,23 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
                         if ((uint32_t)(RS * k + hl) < nvt) b.vars0[v0 + (uint32_t)(RS * k + hl)] = c_var[k];
                 }
                 __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-                // K0a: system scale, summed strictly in reference order (utils.rs:11-33)
-                double scale = 1.0, scale_recip = 1.0;
-                if (prm.mode & 1u) {
-                    double sum = 0.0;
-                    uint32_t count = nvt;
-#pragma unroll
-                    for (int k = 0; k < NC; ++k)
-                        if ((uint32_t)(RS * k) < nvt) seq_add(sum, c_var[k] * c_var[k]);  // (past the end: + 0.0, exact)
-#pragma unroll
-                    for (int k = 0; k < RC; ++k) {
-                        if ((uint32_t)(RS * k) < net) {
-                            const bool isd = (uint32_t)(RS * k + hl) < net && (tagk[k] == FX_TAG_PPD || tagk[k] == FX_TAG_PLD);
-                            count += (uint32_t)__popc(gballot(isd));
-                            seq_add(sum, isd ? c_param[k] * c_param[k] : 0.0);
-                        }
-                    }
-                    scale = ::sqrt(sum / (double)count);
-                    scale_recip = 1.0 / scale;
-                }
+                // K0a: system scale; K0b: the perturbation (gc_setup)
+                double x[NC], pe[RC];
+                const double scale = gc_setup<NC, RC>(prm.mode, nvt, net, hl, gbase, c_var, colk, c_param, tagk, x, pe);
 #pragma unroll
                 for (int k = 0; k < NC; ++k) {
                     const uint32_t i = (uint32_t)(RS * k + hl);
                     if (i < nvt) {
-                        double x = (prm.mode & 1u) ? c_var[k] * scale_recip : c_var[k];
-                        if (colk[k] >= 0 && (prm.mode & 2u)) {  // K0b: two draws of the LCG per free variable, in column order
-                            uint32_t st = lcg_jump(42u, 2u * (uint32_t)colk[k]);
-                            st = st * 1664525u + 1013904223u;
-                            const double f1 = (1.0 / 4294967295.0) * (double)st;
-                            st = st * 1664525u + 1013904223u;
-                            const double f2 = (1.0 / 4294967295.0) * (double)st;
-                            x += x * (1.0 / 8196.0) * f1 + (1.0 / 65568.0) * f2;
-                        }
-                        XS[i] = (T)x;  // (perturbed from the f64 input: the f64 start point is bit-identical to the reference)
+                        XS[i] = (T)x[k];  // (perturbed from the f64 input: the f64 start point is bit-identical to the reference)
                         VOUT[i] = c_var[k];
                         b.vars[v0 + i] = c_var[k];  // fixed variables stay bit-identical
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < RC; ++k) {
-                    const uint32_t i = (uint32_t)(RS * k + hl);
-                    if (i < net) {
-                        double prm_e = c_param[k];
-                        if ((prm.mode & 1u) && (tagk[k] == FX_TAG_PPD || tagk[k] == FX_TAG_PLD)) prm_e = scale_recip * prm_e;
-                        P[i] = (T)prm_e;
-                    }
-                }
+                for (int k = 0; k < RC; ++k)
+                    if ((uint32_t)(RS * k + hl) < net) P[RS * k + hl] = (T)pe[k];
                 if (hl == 0) STASH[0] = scale;
+                }
                 group_sync();
 #pragma unroll
                 for (int q = 0; q < NC; ++q) xc[q] = ((uint32_t)(hl + RS * q) < nfree) ? XS[my_vi[q]] : T(0);
@@ -713,10 +754,22 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
         // (constraints/mod.rs:96-109), the result record =================
         if (finish_now) {
             const uint32_t v0 = b.uniform ? s * nvt : b.var_off[s], e0 = b.uniform ? s * net : b.expr_off[s];
+            const double scale = STASH[0];
+            double sse_u = 0.0;  // (a staged build: gc_close_kernel fills it in)
+            if constexpr (STAGED) {
+#pragma unroll
+                for (int q = 0; q < NC; ++q) {
+                    if ((uint32_t)(hl + RS * q) < nfree) {
+                        const double x = (double)xc[q];
+                        const double xo = (prm.mode & 1u) ? scale * x : x;
+                        b.vars[v0 + my_vi[q]] = xo;
+                        if (b.vars_out) b.vars_out[v0 + my_vi[q]] = xo;
+                    }
+                }
+            } else {
             double c_param[RC];  // the unscaled parameters of expressions hl, hl + 16, ...
 #pragma unroll
             for (int k = 0; k < RC; ++k) c_param[k] = (uint32_t)(RS * k + hl) < net ? b.expr_param[e0 + (uint32_t)(RS * k + hl)] : 0.0;
-            const double scale = STASH[0];
 #pragma unroll
             for (int q = 0; q < NC; ++q) {
                 if ((uint32_t)(hl + RS * q) < nfree) {
@@ -744,7 +797,8 @@ __device__ __forceinline__ void grouped_c_body(const DeviceBatch& b, const LmPar
                     part[k] = r * r;
                 }
             }
-            const double sse_u = rows_sum(part);
+            sse_u = rows_sum(part);
+            }
             if (hl == 0) {
                 fx_result res;
                 res.accepted = accepted;
@@ -773,7 +827,8 @@ struct GcBuild {
     unsigned int* raised;   // (raise_lds_limit_once's per-device bits)
     uint32_t waves_per_cu;  // by registers
 };
-// fx_grouped_band.hip: the two-column f64 kernel with the factor of GC_BANDS[band - 1]; fn == nullptr: no such build
-GcBuild gc_band_build(uint32_t band);
+// fx_grouped_band.hip: the two-column f64 kernel with the factor of GC_BANDS[band - 1] (staged: its build for a staged set-up and
+// closing check); fn == nullptr: no such build
+GcBuild gc_band_build(uint32_t band, bool staged);
 
 }  // namespace fx

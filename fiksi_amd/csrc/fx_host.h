@@ -154,9 +154,11 @@ struct fx_ctx {
     int route_grouped = -1;
     int grouped_one_structure = 1;  // the grouped kernel's build for batches of one structure (FIKSI_AMD_GROUPED_C=0: never)
     int gc_band = 1;                // ... its band-factor instantiations (FIKSI_AMD_GC_BAND=0: the dense factor always)
+    int gc_staged = 1;              // ... the staged set-up and closing check of its two-column f64 kernel (FIKSI_AMD_GC_STAGED=0: never)
     uint32_t grouped_min_systems = 8u;
     int presort = 1;                       // fx_ctx_set_presort
     uint32_t hold_passes = 2u;             // fx_ctx_set_hold_passes
+    bool hold_set = false;                 // ... has been called
     uint32_t ladder = 1u, ladder_k = 8u, ladder_tail = 0xFFFFFFFFu, ladder_spread = 1u;  // fx_ctx_set_ladder
     int wide_routing = -1;                 // fx_ctx_set_wide_routing
     uint32_t sparse_fronts = 1u, sparse_front_ranks = 0u;  // fx_ctx_set_sparse_fronts
@@ -243,8 +245,10 @@ struct fx_ctx {
         p.route_grouped = route_grouped;
         p.grouped_one_structure = grouped_one_structure;
         p.gc_band = gc_band;
+        p.gc_staged = gc_staged;
         p.grouped_min_systems = grouped_min_systems;
         p.hold_passes = hold_passes;
+        p.hold_set = hold_set ? 1 : 0;
         p.ladder = ladder;
         p.ladder_k = ladder_k;
         p.ladder_tail = ladder_tail;
@@ -361,6 +365,7 @@ struct fx_dbatch {
     uint32_t* d_order = nullptr;  // fx_batch_schedule_by_last_solve
     // longest-first hand-out from a scout pass (fx_presort.hip): keys / ids [2][n], the sort's workspace
     float* ps_keys = nullptr;
+    double* gc_stage = nullptr;  // the one-structure build's staging area (DeviceBatch::st_x / st_p / st_scale), on first use: ensure_gc_stage
     uint32_t* ps_ids = nullptr;
     unsigned char* ps_temp = nullptr;
     size_t ps_temp_bytes = 0;
@@ -465,6 +470,7 @@ bool build_qrg_program(const uint8_t* expr_tag, const uint16_t* expr_idx16, cons
 
 // ---- fx_solve.cpp: routing and launches
 int launch_solve_scheduled(fx_ctx* ctx, fx_dbatch* db, const fx::LmParams& p);
+bool gc_stage_wanted(const fx_ctx* ctx, const fx_dbatch* db);
 bool wide_kernel_applies(const fx::LmParams& p);
 int solve_large_systems(fx_ctx* ctx, fx_dbatch* db, const fx::LmParams& p);
 int solve_beyond_one_wavefront(fx_ctx* ctx, fx_dbatch* db, fx::LmParams p);

@@ -23,6 +23,7 @@ hipError_t launch_solve_grouped_general(const DeviceBatch&, const LmParams&, hip
 size_t grouped_lds_bytes(const DeviceBatch&, uint32_t, bool) { return 0; }
 bool grouped_c_applies(const DeviceBatch&, const LmParams&) { return false; }
 int grouped_c_band(const DeviceBatch&, const LmParams&) { return -1; }
+int grouped_c_staged(const DeviceBatch&, const LmParams&) { return -1; }
 hipError_t launch_solve_grouped_c(const DeviceBatch&, const LmParams&, hipStream_t) { return hipErrorNoDevice; }
 size_t grouped_c_lds_bytes(const DeviceBatch&, uint32_t) { return 0; }
 bool grouped_s_applies(const DeviceBatch&, const LmParams&) { return false; }

@@ -128,8 +128,31 @@ static bool launch_class_qr(fx_ctx* ctx, fx_dbatch* db, const fx::LmParams& p, i
     return true;
 }
 
+// The staging area of the one-structure build's set-up and closing check (fx_grouped_c.hip: gc_stage_kernel, gc_close_kernel):
+// for a batch with a program of that build (one structure, or big structure classes) whose values are on the device, from
+// GC_STAGE_MIN_SYSTEMS Systems on — below that the two extra launches cost about what they save. Allocated once per batch.
+constexpr uint32_t GC_STAGE_MIN_SYSTEMS = 2048u;
+bool gc_stage_wanted(const fx_ctx* ctx, const fx_dbatch* db) {
+    const fx::DeviceBatch& d = db->d;
+    const bool two_columns = d.gc_tab ? d.gc_nc == 2u && d.gc_rc == 2u : !db->classes.empty() && db->cl_nc == 2u && db->cl_rc == 2u;
+    return ctx->gc_staged && !db->in_place && d.n_systems >= GC_STAGE_MIN_SYSTEMS && two_columns;
+}
+static int ensure_gc_stage(fx_ctx* ctx, fx_dbatch* db) {
+    fx::DeviceBatch& d = db->d;
+    if (db->gc_stage || !gc_stage_wanted(ctx, db)) return FX_OK;
+    // (32 start values, 32 parameters, the scale and the System number per place: 65.5 doubles)
+    int rc = dev_alloc_copy(ctx, db, &db->gc_stage, (const double*)nullptr, (size_t)d.n_systems * 66u);
+    if (rc) return rc;
+    d.st_x = db->gc_stage;
+    d.st_p = d.st_x + (size_t)d.n_systems * 32u;
+    d.st_scale = d.st_p + (size_t)d.n_systems * 32u;
+    d.st_sys = reinterpret_cast<uint32_t*>(d.st_scale + d.n_systems);
+    return FX_OK;
+}
+
 int launch_solve_scheduled(fx_ctx* ctx, fx_dbatch* db, const fx::LmParams& p) {
     fx::DeviceBatch& d = db->d;
+    if (int rc = ensure_gc_stage(ctx, db)) return rc;
     // (every System beyond one wavefront — one System::solve on a large sketch is such a batch: the one-wavefront kernels would be
     // launched to find nothing of theirs; solve_beyond_one_wavefront has them all)
     // (SinglePass: the launch below also starts the block walker of large Systems whose blocks fit one wavefront)

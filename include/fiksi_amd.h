@@ -236,7 +236,9 @@ int fx_ctx_set_routing(fx_ctx* ctx, int grouped, uint32_t grouped_min_systems);
 int fx_ctx_set_presort(fx_ctx* ctx, int enable, uint32_t min_systems);
 /* Grouped kernel: a row of a wavefront that has finished its System (SinglePass: its block) waits up to `passes` trial passes (default 2) for a
  * second row to finish, so that the two take their next Systems side by side — the hand-over blocks cost the wavefront
- * the same for one row as for four. 0: never wait. Scheduling only: every System's result is the same bits either way. */
+ * the same for one row as for four. 0: never wait. Until this is called, a launch whose set-up and closing check are staged
+ * outside the kernel (fx_debug_grouped_staged) does not wait: its hand-over is a few loads and stores. Scheduling only: every
+ * System's result is the same bits either way. */
 int fx_ctx_set_hold_passes(fx_ctx* ctx, uint32_t passes);
 /* Batches whose Systems all have ONE structure (one component) run builds of the grouped kernel made for them: up to 48 free
  * variables fx_grouped_c.hip (the structure's lists shared by a wavefront, Jt J by its pattern, up to four wavefronts per SIMD:
@@ -372,6 +374,11 @@ int fx_debug_grouped_build(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* op
  * few dense last rows (the structure's factor fits it; same bits), -1 = the launch is not that kernel. A context created under
  * FIKSI_AMD_GC_BAND=0 takes the dense factor always. Launches nothing. */
 int fx_debug_grouped_factor(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, int* band);
+/* Diagnostic only: whether build 1 or 3's solve (fx_debug_grouped_build) sets up every System (scale, perturbed start point, scaled
+ * parameters) in a streaming pass before its two-column f64 kernel and runs the closing check in a pass after it: 1 = staged, 0 = the
+ * kernel does both itself (same bits), -1 = the solve is neither build. Staged: resident batches of 2 048 Systems and more with their
+ * values on the device. A context created under FIKSI_AMD_GC_STAGED=0 never stages. Launches nothing. */
+int fx_debug_grouped_staged(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, int* staged);
 /* Host only, no device needed: the Cholesky factor of the normal matrix of System `system`, taken as one component, in the column
  * order of build 1's program (its free variables ascending, then identity padding up to *n = 16, 32 or 48 columns): first[i] =
  * row i's first structural non-zero column, fill included (first holds 48 bytes); *band = the factor build that launch takes as

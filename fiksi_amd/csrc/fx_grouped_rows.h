@@ -105,13 +105,24 @@ struct RStep {  // one column step of the factorization / of a triangular solve
     template <bool FWD>
     static __device__ __forceinline__ void factor(T (&a)[NC][N], T (&invd)[NC], T (&acc)[NC], bool& bad, int hl, int kmax) {
         {
+        static_assert(!(FWD && BOUNDED), "the fused build runs every step: RBlock::factor checks every lane's pivot");
         const T piv = rbcast<KL>(a[KA][K]);
-        bad = bad || !(piv > T(0)) || !(piv < Lim<T>::huge());
+        if constexpr (FWD) {
+            // the fused build needs no invd during the factor (forward_dpp takes rs), so invd[KA] collects the pivots
+            // instead, and RBlock::factor checks them and turns them into invd once all steps are done (pivots_close).
+            // Lanes at or above KL take their own a[KA][K] — lane KL's is piv — and later steps of the array overwrite
+            // only lanes above: lane j keeps the pivot of step j. (hl > KL - 1 is the mask of the step before: every lane
+            // predicate of the factor and of backward is hl > k, one family that fits in SGPRs, where three spilled.)
+            if (hl > KL - 1) invd[KA] = a[KA][K];
+        } else {
+            bad = bad || !(piv > T(0)) || !(piv < Lim<T>::huge());
+        }
         const T rs = rsqrt_refined(piv);
         const T ip = rs * rs;  // 1/pivot
         // a band factor: 1/pivot overflows on a denormal pivot, and then the dense factor's next pivot is NaN or -inf (it
         // updates row K + 1 with mul = inf or 0 * inf); the band factor may skip that update, so it says `bad` here
-        if constexpr (Band::SKIPS && K < N - 1) bad = bad || !(ip < Lim<T>::huge());
+        // (the fused build: in pivots_close, from the same rs * rs)
+        if constexpr (!FWD && Band::SKIPS && K < N - 1) bad = bad || !(ip < Lim<T>::huge());
         T mul[NC];
 #pragma unroll
         for (int q = 0; q < NC; ++q) {
@@ -120,8 +131,14 @@ struct RStep {  // one column step of the factorization / of a triangular solve
             const T ljk = a[q][K] * rs;
             const bool above = (q > KA) || (hl > KL);  // column > K
             mul[q] = above ? a[q][K] * ip : T(0);
-            if (above || hl == KL) a[q][K] = ljk;
-            if (q == KA && hl == KL) invd[q] = rs;
+            if constexpr (FWD) {
+                // the diagonal entry keeps the pivot: no step and no pass reads a[KA][K] of lane KL again (later steps
+                // read rows above K, forward_dpp and backward leave lane KL out)
+                if (above) a[q][K] = ljk;
+            } else {
+                if (above || hl == KL) a[q][K] = ljk;
+                if (q == KA && hl == KL) invd[q] = rs;
+            }
         }
         // a[q][i] -= A_iK (from the lane of column K, which still holds A_iK = L_iK * d_K) * mul[q]: ONE instruction
         // each, v_fmac_f64_dpp with the broadcast as its DPP operand. Array KA last: its update leaves the lane of
@@ -159,6 +176,23 @@ struct RStep {  // one column step of the factorization / of a triangular solve
         }
         }
     }
+    // FWD, after the last step: the pivot checks of all steps at once, and invd from the pivots. Lane j of invd[q] holds the
+    // pivot of step 16 q + j (factor); the checks are those the other builds make step by step, and rs is the same function
+    // of the same pivot, so the verdict and invd are what they would be. `bad` says whether any lane of the row failed.
+    static __device__ __forceinline__ void pivots_close(T (&invd)[NC], bool& bad, int hl) {
+        bool lane_bad = false;
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            const T piv = invd[q];
+            lane_bad = lane_bad || !(piv > T(0)) || !(piv < Lim<T>::huge());
+            const T rs = rsqrt_refined(piv);
+            invd[q] = rs;
+            // (the step-by-step ip test of a band factor, K < N - 1)
+            if constexpr (Band::SKIPS)
+                if (q < NC - 1 || hl < RS - 1) lane_bad = lane_bad || !(rs * rs < Lim<T>::huge());
+        }
+        bad = bad || ((__ballot(lane_bad) >> (__lane_id() & ~(RS - 1))) & 0xFFFFull) != 0ull;
+    }
     // acc[q] -= a[q][K] * y_K, y_K = (acc * invd) of column K's lane: the broadcast is the DPP operand of the
     // multiply-add; lanes that must not take part get a zero factor.
     static __device__ __forceinline__ void forward_dpp(const T (&a)[NC][N], T invd_k, T (&acc)[NC], int hl) {
@@ -194,7 +228,8 @@ struct RStep {  // one column step of the factorization / of a triangular solve
 #pragma unroll
             for (int q = 0; q <= KA; ++q) {
                 if (q == KA && KL == 0) continue;  // no column of this array lies below K
-                const T w = (q < KA || hl < KL) ? a[q][K] : T(0);
+                // (column < K, written as the complement of the factor's mask hl > KL - 1: one family of lane masks)
+                const T w = (q == KA && hl > KL - 1) ? T(0) : a[q][K];
                 fnma_rbcast<KL>(acc[q], t, w);
             }
         } else {
@@ -235,6 +270,7 @@ struct RBlock {
     static __device__ __forceinline__ void factor(T (&a)[NC][N], T (&invd)[NC], T (&acc)[NC], bool& bad, int hl, int kmax) {
         if (!BOUNDED || 8 * KB < kmax) factor8<FWD>(a, invd, acc, bad, hl, kmax, std::make_integer_sequence<int, 8>{});
         if constexpr (8 * KB + 8 < N) RBlock<NC, T, KB + 1, BOUNDED, W, B>::template factor<FWD>(a, invd, acc, bad, hl, kmax);
+        if constexpr (FWD && KB == 0) RStep<NC, T, 0, BOUNDED, W, B>::pivots_close(invd, bad, hl);
     }
     static __device__ __forceinline__ void forward(const T (&a)[NC][N], const T (&invd)[NC], T (&acc)[NC], int hl, int kmax) {
         if (!BOUNDED || 8 * KB < kmax) forward8(a, invd, acc, hl, kmax, std::make_integer_sequence<int, 8>{});

@@ -136,6 +136,7 @@ extern "C" {
     pub fn fx_debug_grouped_staged(ctx: *mut fx_ctx, db: *mut fx_dbatch, opts: *const fx_solving_opts, staged: *mut c_int) -> c_int;
     pub fn fx_gc_factor_profile(batch: *const fx_batch, system: u32, n: *mut u32, first: *mut u8, band: *mut c_int) -> c_int;
     pub fn fx_debug_ctx_plan_bytes(ctx: *mut fx_ctx, bytes: *mut u64) -> c_int;
+    pub fn fx_debug_dense_solve(ctx: *mut fx_ctx, variant: c_int, count: u32, n: u32, A: *const f64, b: *const f64, kmax: u32, x: *mut f64, bad: *mut i32) -> c_int;
     pub fn fx_system_solve_batch(ctx: *mut fx_ctx, batch: *const fx_batch, opts: *const fx_solving_opts, results: *mut fx_result) -> c_int;
     pub fn fx_host_register(ctx: *mut fx_ctx, ptr: *mut c_void, bytes: usize) -> c_int;
     pub fn fx_host_unregister(ctx: *mut fx_ctx, ptr: *mut c_void) -> c_int;

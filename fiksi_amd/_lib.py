@@ -142,6 +142,7 @@ SIGNATURES = [
     ("fx_debug_grouped_staged", C.c_int, [_vp, _vp, C.POINTER(FxSolvingOpts), C.POINTER(C.c_int)]),
     ("fx_gc_factor_profile", C.c_int, [C.POINTER(FxBatch), C.c_uint32, C.POINTER(C.c_uint32), _vp, C.POINTER(C.c_int)]),
     ("fx_debug_ctx_plan_bytes", C.c_int, [_vp, u64p]),
+    ("fx_debug_dense_solve", C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     ("fx_timer_begin", C.c_int, [_vp]),
     ("fx_timer_end", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("fx_system_solve_batch", C.c_int, [_vp, C.POINTER(FxBatch), C.POINTER(FxSolvingOpts), _vp]),

@@ -3,6 +3,7 @@ HBM-resident batches. All numerics happen in the HIP kernels behind the ABI."""
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import Dict, Optional
 
 import numpy as np
@@ -24,6 +25,45 @@ HINT_ONE_STRUCTURE = 1  # (FX_HINT_ONE_STRUCTURE)
 (VARIABLE_VARIABLE_EQUALITY, POINT_POINT_DISTANCE, POINT_POINT_POINT_ANGLE, POINT_LINE_INCIDENCE,
  POINT_LINE_DISTANCE, POINT_CIRCLE_INCIDENCE, SEGMENT_SEGMENT_LENGTH_EQUALITY, LINE_LINE_ANGLE,
  LINE_LINE_PARALLELISM, LINE_LINE_PERPENDICULARITY, LINE_CIRCLE_TANGENCY) = range(11)
+
+
+class DenseVariant(namedtuple("DenseVariant", "id kind n dtype bounded w b fwd site")):
+    """One instantiation of the LM step's register Cholesky (fx_debug_dense_solve). kind: "rows" (fx_grouped_rows.h, four
+    matrices per wavefront), "chol" (fx_chol.h, fx_kernels.hip) or "wide" (fx_chol.h, a diagonal block of fx_wide.hip); n: the
+    size it factors; w, b: the band (half-width, dense last rows; w = n is dense); site: "general" (fx_grouped.hip) or "one"
+    (fx_grouped_c.h) for rows, "b1" / "b2" (first block; second block, factored and solved with nb) for wide."""
+    __slots__ = ()
+
+    @property
+    def name(self) -> str:
+        t = "f32" if self.dtype == np.float32 else "f64"
+        if self.kind == "rows":
+            band = f"_band{self.w}_{self.b}" if self.w < self.n else ""
+            return f"rows_{self.site}_nc{self.n // 16}_{t}{'_bounded' if self.bounded else ''}{'_fwd' if self.fwd else ''}{band}"
+        if self.kind == "chol":
+            return f"chol{self.n}_{t}"
+        return f"wide_{self.site}"
+
+
+def _dense_variants():
+    v = []
+    for bounded in (False, True):  # fx_grouped.hip: launch_solve_grouped_general
+        for dt in (np.float64, np.float32):
+            for nc in (1, 2, 3):
+                v.append(DenseVariant(len(v), "rows", 16 * nc, dt, bounded, 16 * nc, 0, False, "general"))
+    for nc, dt, w, b in ((1, np.float64, 16, 0), (2, np.float64, 32, 0), (2, np.float32, 32, 0), (3, np.float64, 48, 0),
+                         (2, np.float64, 5, 0), (2, np.float64, 5, 4), (2, np.float64, 5, 6)):  # fx_grouped_c.h, FWD = (NC == 2)
+        v.append(DenseVariant(len(v), "rows", 16 * nc, dt, False, w, b, nc == 2, "one"))
+    for dt in (np.float64, np.float32):  # fx_kernels.hip
+        for n in range(8, 65, 8):
+            v.append(DenseVariant(len(v), "chol", n, dt, False, n, 0, False, ""))
+    for site in ("b1", "b2"):  # fx_wide.hip
+        v.append(DenseVariant(len(v), "wide", 64, np.float64, False, 64, 0, False, site))
+    return tuple(v)
+
+
+# the variants of fx_debug_dense_solve, in the order of its switch (fx_debug_chol.hip)
+DENSE_VARIANTS = _dense_variants()
 
 _FIELDS = {
     "var_off": np.uint32, "expr_off": np.uint32, "vars": np.float64, "var_fixed": np.uint8,
@@ -268,6 +308,20 @@ class Context:
         b = C.c_uint64(0)
         check(lib.fx_debug_ctx_plan_bytes(self._h, C.byref(b)), "fx_debug_ctx_plan_bytes")
         return int(b.value)
+
+    def dense_solve(self, variant: int, A: np.ndarray, b: np.ndarray, kmax: int = 0):
+        """Diagnostic: x = A^-1 b per matrix through one build's register Cholesky (fx_debug_dense_solve; DENSE_VARIANTS).
+        A: (count, n, n), b: (count, n), float64. Returns (x, bad) with bad[i] True where the factor said singular."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        count, n = b.shape
+        if A.shape != (count, n, n):
+            raise ValueError("A must be (count, n, n) for b of shape (count, n)")
+        x = np.empty((count, n), dtype=np.float64)
+        bad = np.empty(count, dtype=np.int32)
+        check(lib.fx_debug_dense_solve(self._h, int(variant), count, n, A.ctypes.data, b.ctypes.data, int(kmax), x.ctypes.data,
+                                       bad.ctypes.data), "fx_debug_dense_solve")
+        return x, bad != 0
 
     def timer_begin(self):
         check(lib.fx_timer_begin(self._h), "fx_timer_begin")

@@ -652,6 +652,52 @@ int fx_debug_ctx_plan_bytes(fx_ctx* ctx, uint64_t* bytes) try {
 }
 FX_CATCH_CODE
 
+int fx_debug_dense_solve(fx_ctx* ctx, int variant, uint32_t count, uint32_t n, const double* A, const double* b, uint32_t kmax, double* x,
+                         int32_t* bad) try {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (count == 0u) return FX_OK;
+    const uint32_t N = fx::debug_dense_size(variant);
+    if (!A || !b || !x || !bad || n == 0u || N == 0u || n > N || count > (1u << 16)) return fail(FX_ERR_INVALID, "bad argument");
+    // the kernels read N x N blocks, four to a wavefront: the caller's matrices padded with the identity, the count with identities
+    const uint32_t cp = (count + 3u) / 4u * 4u;
+    std::vector<double> hA((size_t)cp * N * N, 0.0), hb((size_t)cp * N, 0.0), hx((size_t)cp * N);
+    std::vector<int32_t> hbad(cp);
+    for (uint32_t g = 0; g < cp; ++g) {
+        double* Ag = hA.data() + (size_t)g * N * N;
+        for (uint32_t i = 0; i < N; ++i) Ag[(size_t)i * N + i] = 1.0;
+        if (g >= count) continue;
+        for (uint32_t i = 0; i < n; ++i) {
+            for (uint32_t j = 0; j < n; ++j) Ag[(size_t)i * N + j] = A[((size_t)g * n + i) * n + j];
+            hb[(size_t)g * N + i] = b[(size_t)g * n + i];
+        }
+    }
+    double *dA = nullptr, *db_ = nullptr, *dx = nullptr;
+    int32_t* dbad = nullptr;
+    hipError_t e = hipMalloc((void**)&dA, hA.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&db_, hb.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&dx, hx.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&dbad, cp * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpyAsync(dA, hA.data(), hA.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db_, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = fx::launch_debug_dense_solve(variant, cp, n, dA, db_, kmax, dx, dbad, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hx.data(), dx, hx.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hbad.data(), dbad, cp * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(dA);
+    (void)hipFree(db_);
+    (void)hipFree(dx);
+    (void)hipFree(dbad);
+    if (e == hipErrorInvalidValue) return fail(FX_ERR_INVALID, "variant %d does not take n = %u, kmax = %u", variant, n, kmax);
+    if (e != hipSuccess) return fail(FX_ERR_HIP, "dense solve failed: %s", hipGetErrorString(e));
+    for (uint32_t g = 0; g < count; ++g) {
+        for (uint32_t i = 0; i < n; ++i) x[(size_t)g * n + i] = hx[(size_t)g * N + i];
+        bad[g] = hbad[g];
+    }
+    return FX_OK;
+}
+FX_CATCH_CODE
+
 // Diagnostic (not part of the drop-in surface): runs the stamped build of the fused kernel once and
 // returns the shader cycles summed over all wavefronts for {setup, eval, form, factor, solve, tail}.
 int fx_debug_phase_cycles(fx_ctx* ctx, fx_dbatch* db, const fx_solving_opts* opts, uint64_t cycles[6]) try {

@@ -119,10 +119,11 @@ struct RStep {  // one column step of the factorization / of a triangular solve
         }
         const T rs = rsqrt_refined(piv);
         const T ip = rs * rs;  // 1/pivot
-        // a band factor: 1/pivot overflows on a denormal pivot, and then the dense factor's next pivot is NaN or -inf (it
-        // updates row K + 1 with mul = inf or 0 * inf); the band factor may skip that update, so it says `bad` here
-        // (the fused build: in pivots_close, from the same rs * rs)
-        if constexpr (!FWD && Band::SKIPS && K < N - 1) bad = bad || !(ip < Lim<T>::huge());
+        // a band factor: 1/pivot overflows to +inf on a denormal pivot, and then the dense factor's next pivot is NaN or -inf
+        // (it updates row K + 1 with mul = inf or 0 * inf); the band factor may skip that update, so it says `bad` here
+        // (the fused build: in pivots_close, from the same rs * rs). Only the overflow: a finite 1/pivot above huge() leaves
+        // the dense factor finite, and the band factor goes on with it.
+        if constexpr (!FWD && Band::SKIPS && K < N - 1) bad = bad || !(ip < T(__builtin_huge_val()));
         T mul[NC];
 #pragma unroll
         for (int q = 0; q < NC; ++q) {
@@ -187,9 +188,9 @@ struct RStep {  // one column step of the factorization / of a triangular solve
             lane_bad = lane_bad || !(piv > T(0)) || !(piv < Lim<T>::huge());
             const T rs = rsqrt_refined(piv);
             invd[q] = rs;
-            // (the step-by-step ip test of a band factor, K < N - 1)
+            // (the step-by-step ip test of a band factor, K < N - 1: 1/pivot overflowed to +inf)
             if constexpr (Band::SKIPS)
-                if (q < NC - 1 || hl < RS - 1) lane_bad = lane_bad || !(rs * rs < Lim<T>::huge());
+                if (q < NC - 1 || hl < RS - 1) lane_bad = lane_bad || !(rs * rs < T(__builtin_huge_val()));
         }
         bad = bad || ((__ballot(lane_bad) >> (__lane_id() & ~(RS - 1))) & 0xFFFFull) != 0ull;
     }

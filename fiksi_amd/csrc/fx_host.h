@@ -479,3 +479,11 @@ int solve_host(fx_ctx* ctx, const fx_batch* batch, const fx_solving_opts* sopts,
                bool no_hint = false);
 
 }  // namespace fxh
+
+namespace fx {
+// the register Cholesky of one build on given matrices (fx_debug_chol.hip; fx_debug_dense_solve): count a multiple of 4, the
+// matrices padded to debug_dense_size(variant) with the identity
+uint32_t debug_dense_size(int variant);
+hipError_t launch_debug_dense_solve(int variant, uint32_t count, uint32_t n, const double* A, const double* b, uint32_t kmax, double* x,
+                                    int32_t* bad, hipStream_t stream);
+}  // namespace fx

@@ -17,6 +17,10 @@ hipError_t launch_dense_jacobian(const DeviceBatch&, const double*, const uint16
 hipError_t launch_solve_wide(const DeviceBatch&, const LmParams&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_solve_wide_qr(const DeviceBatch&, const LmParams&, hipStream_t) { return hipErrorNoDevice; }
 size_t wide_qr_lds_bytes(uint32_t, uint32_t, uint32_t, uint32_t) { return 0; }
+uint32_t debug_dense_size(int) { return 0; }
+hipError_t launch_debug_dense_solve(int, uint32_t, uint32_t, const double*, const double*, uint32_t, double*, int32_t*, hipStream_t) {
+    return hipErrorNoDevice;
+}
 bool grouped_applies(const DeviceBatch&, const LmParams&) { return false; }
 hipError_t launch_solve_grouped(const DeviceBatch&, const LmParams&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_solve_grouped_general(const DeviceBatch&, const LmParams&, hipStream_t) { return hipErrorNoDevice; }

@@ -388,6 +388,12 @@ int fx_gc_factor_profile(const fx_batch* batch, uint32_t system, uint32_t* n, ui
  * their value slabs: what their index arenas have handed out up to the mark, plus their offset tables' buffers. The same after
  * any number of calls on structures the cache already holds, wherever in the batch they sit. Launches nothing, waits for nothing. */
 int fx_debug_ctx_plan_bytes(fx_ctx* ctx, uint64_t* bytes);
+/* Diagnostic only: the LM step's register Cholesky of one build, run on `count` given n x n row-major matrices A (padded with the
+ * identity up to the build's size) and right-hand sides b: x = A^-1 b as that build computes it, bad[i] = 1 where its factor
+ * reports the matrix singular (x is written either way). `variant` numbers the instantiations the kernels use (fiksi_amd/abi.py:
+ * DENSE_VARIANTS); kmax bounds the SinglePass variants' steps (a multiple of 8, at least n), the others ignore it. Synchronous. */
+int fx_debug_dense_solve(fx_ctx* ctx, int variant, uint32_t count, uint32_t n, const double* A, const double* b, uint32_t kmax, double* x,
+                         int32_t* bad);
 
 /* ---- host-buffer entry points (upload -> run -> download; PCIe inclusive) ------------------- */
 /* == assemble::solve: batch->vars in: unscaled values, out: solved values. results may be NULL.

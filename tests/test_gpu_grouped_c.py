@@ -51,7 +51,10 @@ def _cases():
             # 40 / 46 variables whose factor fills in: the 48-column register build (a sparse factor of that size — the hinged
             # chains of 8 ... 11 triangles — goes to fx_grouped_s.hip: tests/test_gpu_grouped_s.py)
             ("ring20_chords", workloads.ring_chords(1000, 20, 7), {}), ("ring23_chords", workloads.ring_chords(1501, 23, 9), {}),
-            ("every_kind", _mixed_uniform(1500, False), {}), ("every_kind_some_fixed", _mixed_uniform(1500, True), {})]
+            ("every_kind", _mixed_uniform(1500, False), {}), ("every_kind_some_fixed", _mixed_uniform(1500, True), {}),
+            # λ = 1e-300 on a sketch free to move rigidly: trials whose factor is singular (the fused build's pivots_close
+            # against the general build's step-by-step checks)
+            ("ring16_singular_trials", workloads.ring16(2000), {"lambda0": 1e-300})]
 
 
 def test_which_batches_take_the_one_structure_build(fiksi, ctx, ctx_general):

@@ -37,6 +37,7 @@ def _cases():
             "ring16_inconsistent": (lambda: workloads.ring16(3000, inconsistent=True), {}, 1),
             "ring16_trial_cap": (lambda: workloads.ring16(2500), {"max_trials": 21}, 1),
             "ring16_no_perturbation": (lambda: workloads.ring16(2100), {"perturb": False}, 1),
+            "ring16_singular_trials": (lambda: workloads.ring16(2100), {"lambda0": 1e-300}, 1),
             "two_interleaved_structures": (lambda: workloads.ring16_two_structures(6000), {}, 3)}
 
 
